@@ -24,6 +24,17 @@ N>1 GPUs: one process per GPU (torchrun), no data-path collective; RCCL
 (torch.distributed nccl) only reduces the timing and sample counters after
 the timed region.  value = all input samples of all ranks / max-over-ranks
 wall time.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline
+figure needs and no more: set-up, W warm-up steps, N timed steps, the result
+line (the dominant kernel's HIP-event time rides inside the timed steps of a
+one-launch workload, as it always has, so its roofline figure costs no run of
+its own).  `--dump-outputs DIR` adds the arrays the last timed step returned.
+Everything else -- the oracle check, the secondary workloads, the live PMC
+traffic passes, the chunked drop-in timings, the separate profiled pass of a
+chunked workload and the CPU baseline -- runs under `--full` only, where the
+finer switches (--secondary, --no-pmc, --no-streaming, --no-cpu-baseline,
+--check-seconds) select among them.
 """
 import argparse
 import json
@@ -388,6 +399,52 @@ def secondary_default(primary, world):
     return ["ns256", "cfg3", "cfg5", "cfg4", "cfg2_f64", "ns256_f64"] if world == 1 else ["cfg4"]
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # all files of one --dump-outputs directory together (< 64 MB)
+DUMP_SEED = 20240607
+
+
+def sample_rows(n, k):
+    """The fixed sample of k of n rows kept when an output is larger than its share of the dump
+    budget: the first and the last k/4 rows whole (the start-up transient and the end of the
+    stream), and between them one seeded row out of every equal stride.  Sorted, no repeats, a
+    function of (n, k) alone -- two builds dump the same rows."""
+    h = k // 4
+    m = k - 2 * h
+    stride = (n - 2 * h) // m
+    rng = np.random.default_rng(DUMP_SEED)
+    mid = h + np.arange(m, dtype=np.int64) * stride + rng.integers(0, stride, m)
+    return np.concatenate([np.arange(h, dtype=np.int64), mid, np.arange(n - h, n, dtype=np.int64)])
+
+
+def dump_outputs(torch, directory, arrays, rank, world):
+    """Write what the last timed step returned to its caller as DIR/<name>.npy (float64 for
+    float64 outputs, float32 otherwise; int16 PCM as float32 sample values).  An array beyond
+    its share of DUMP_BUDGET_BYTES is written as the sample_rows() rows of it."""
+    os.makedirs(directory, exist_ok=True)
+    sizes = {name: a.numel() * (8 if a.dtype == torch.float64 else 4) for name, a in arrays.items()}
+    left = DUMP_BUDGET_BYTES - 256 * len(arrays)  # .npy headers
+    whole = sum(sizes.values()) <= left
+    info = {}
+    # smallest first: a small array (the flush tail) is written whole, the rest share what remains equally
+    for i, name in enumerate(sorted(arrays, key=sizes.get)):
+        a = arrays[name]
+        odt = torch.float64 if a.dtype == torch.float64 else torch.float32
+        n = a.shape[0]
+        row_bytes = max(sizes[name] // max(n, 1), 1)
+        k = min(n, (left // (len(arrays) - i)) // row_bytes)
+        left -= k * row_bytes
+        if 0 < k < n:
+            a = a[torch.from_numpy(sample_rows(n, k)).to(a.device)]
+        fname = name + (f"_rank{rank}" if world > 1 else "") + ".npy"
+        np.save(os.path.join(directory, fname), a[:k].to(odt).cpu().numpy())
+        info[fname] = {"frames": n, "frames_written": k, "channels": int(a.shape[1]),
+                       "dtype": str(odt).replace("torch.", "")}
+    return {"dir": directory, "files": info,
+            "sample": "whole arrays" if whole else
+                      f"rows of sample_rows(frames, frames_written), seed {DUMP_SEED}: first and last quarter of the "
+                      "sample contiguous at the stream's ends, the rest one row per equal stride between them"}
+
+
 def run_workload(key, args, steps, warmup, world, rank, dev, primary):
     """Time `steps` steps (after `warmup`) of workload `key` on this rank; returns its JSON
     object (value = all ranks' input samples / max-over-ranks wall time) and the dominant
@@ -495,7 +552,10 @@ def run_workload(key, args, steps, warmup, world, rank, dev, primary):
     sync()
     barrier()
     t1 = time.perf_counter()
-    if not dry and not inline_prof:  # a separate profiled pass (the timed steps carry no event packets)
+    dumped = None
+    if primary and args.dump_outputs:  # what the last timed step handed its caller: Process frames, Flush tail
+        dumped = dump_outputs(torch, args.dump_outputs, {"process": y[:n_proc], "flush": yf[:n_tail]}, rank, world)
+    if not dry and not inline_prof and args.full:  # a separate profiled pass (the timed steps carry no event packets)
         r.profile(True)
         for k in range(6):
             r.profile_read(k)
@@ -546,13 +606,16 @@ def run_workload(key, args, steps, warmup, world, rank, dev, primary):
         "input_samples_total": int(total_samples / steps),
         "local_ms_per_step": round(local_ms, 4),
     }
+    if dumped:
+        obj["outputs"] = dumped
     kernel_keys = []
-    if not dry:
+    if not dry and (inline_prof or args.full):  # a plain run of a chunked workload took no kernel events
         roof, kernel_keys = roofline(w, key, gar, r, prof, steps, frames, C, n_proc, n_tail)
         obj["roofline"] = roof
         roof["kernel_timing"] = ((f"HIP events around the launches of every {int(os.environ.get('GAR_BENCH_EVENT_EVERY', '4'))}th "
                                   "timed step, inside the timed region, on the launch stream") if inline_prof
                                  else "HIP events around each launch, in a separate pass after the timed steps")
+    if not dry:
         obj["arith"] = (("int16 PCM I/O converted in the kernel's loads (float64(i)/32767 -> f32) and stores "
                          "(clamp, x32767, truncate); rms_vs_oracle in full-scale units includes the output "
                          "quantization (~0.6 LSB = 1.8e-5); " if pcm_scale else "f32 I/O; ") +
@@ -762,8 +825,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs (ranks) of one node; without torchrun, N > 1 starts N ranks itself")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: oracle check, secondary workloads, PMC "
+                         "traffic passes, chunked drop-in timings, the profiled pass of a chunked workload, CPU "
+                         "baseline (the switches below choose among them; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the arrays the last step returned (Process frames, Flush "
+                         "tail) as DIR/process.npy and DIR/flush.npy, float32 or float64, at most 60 MB in all "
+                         "(a fixed seeded row sample of a larger array)")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--seconds", type=float, default=None, help="stream length override (primary workload)")
     ap.add_argument("--secondary", default="auto",
@@ -778,6 +849,13 @@ def main():
                     help="no GPU: dry-run handles (exact host state machine) over gloo -- the multi-rank "
                          "sharding and reduction end to end on CPU (tests/test_dist.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU path (a dry run computes no samples)")
+    if not args.full:  # a plain run: the primary workload's timed steps and nothing beside them
+        args.secondary, args.check_seconds = "none", 0.0
+        args.no_cpu_baseline = args.no_pmc = args.no_streaming = True
     launch_ranks(args, sys.argv[1:])
 
     world, rank, local = dist_env()
@@ -827,6 +905,7 @@ def main():
         line["cpu_baseline"] = cpu_baseline(WORKLOADS[args.workload], target_s=args.cpu_baseline_seconds)
     if args.dry_run:
         line["dry_run"] = True
+    line["full"] = args.full
     line["native_lib"] = native_lib_info()
     if rank == 0:
         print(json.dumps(front_keys(line)), flush=True)

@@ -127,7 +127,7 @@ def test_bench_main_two_ranks_dry_run():
     handles = the exact host state machine): cfg4's 1024 streams sharded one NewBatch per
     rank, the counters reduced over ranks, equal the single-rank totals; the weak-scaled
     secondary (cfg5 per rank) doubles."""
-    extra = ["--workload", "cfg4", "--seconds", "0.5", "--secondary", "cfg5"]
+    extra = ["--full", "--workload", "cfg4", "--seconds", "0.5", "--secondary", "cfg5"]
     one = _run_bench(1, extra)
     two = _run_bench(2, extra)
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1
@@ -175,7 +175,7 @@ def test_bench_two_ranks_line_carries_cpu_baseline_and_per_rank():
     baseline after the timed regions (here a bounded 0.3 s sample), and the line lists every rank's
     own step time and kernel figures (all_gather over the process group)."""
     import json
-    p = _bench_cmd(["--dry-run", "--gpus", "2", "--workload", "cfg2", "--seconds", "0.5", "--secondary", "cfg4",
+    p = _bench_cmd(["--full", "--dry-run", "--gpus", "2", "--workload", "cfg2", "--seconds", "0.5", "--secondary", "cfg4",
                     "--steps", "2", "--warmup", "1", "--cpu-baseline-seconds", "0.3"])
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${TAG:-ab}; mkdir -p $O; cd $R
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in ${LIBS}; do
     GAR_LIB_PATH=$R/go-audio-resampler_amd/$lib timeout -k 10 300 python3 bench.py --workload ${WL:-cfg2} --steps ${STEPS:-10} --warmup 3 \
-      --no-cpu-baseline --no-pmc --no-streaming --check-seconds 0 --secondary ${SEC:-none} > $O/run.json 2> $O/run.err || { tail -20 $O/run.err; exit 1; }
+      --full --no-cpu-baseline --no-pmc --no-streaming --check-seconds 0 --secondary ${SEC:-none} > $O/run.json 2> $O/run.err || { tail -20 $O/run.err; exit 1; }
     python3 - "$O/run.json" "$lib" "$r" <<'PY' | tee -a $O/ab.txt
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

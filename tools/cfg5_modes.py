@@ -8,7 +8,7 @@ import sys
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 p = subprocess.run([sys.executable, os.path.join(R, "bench.py"), "--workload", "cfg5", "--steps", "4", "--warmup", "2",
-                    "--no-cpu-baseline", "--no-pmc", "--no-streaming", "--check-seconds", "0", "--secondary", "none"],
+                    "--full", "--no-cpu-baseline", "--no-pmc", "--no-streaming", "--check-seconds", "0", "--secondary", "none"],
                    capture_output=True, text=True, timeout=300)
 if p.returncode:
     sys.stderr.write(p.stderr[-3000:])

@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${TAG:-dbg}; mkdir -p $O; cd $R
 for m in ${MODES:-0 16}; do
   env ${DBGVAR:-GAR_HXS_DBG}=$m GAR_LIB_PATH=$R/go-audio-resampler_amd/${LIB:-libgar_dev.so} timeout -k 10 300 python3 bench.py --workload ${WL:-ns256} \
-    --steps ${STEPS:-6} --warmup 2 --no-cpu-baseline --no-pmc --no-streaming --check-seconds 0 --secondary none > $O/run.json 2> $O/run.err || { tail -20 $O/run.err; exit 1; }
+    --steps ${STEPS:-6} --warmup 2 --full --no-cpu-baseline --no-pmc --no-streaming --check-seconds 0 --secondary none > $O/run.json 2> $O/run.err || { tail -20 $O/run.err; exit 1; }
   python3 - "$O/run.json" "$m" <<'PY' | tee -a $O/modes.txt
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

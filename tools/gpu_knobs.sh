@@ -6,7 +6,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for k in $KNOBS; do
     e=""; [ "$k" = default ] || e="${k//,/ }"
     env $e timeout -k 10 200 python3 bench.py --workload ${WL:-ns256} --steps ${STEPS:-8} --warmup 3 --no-cpu-baseline --no-pmc \
-      --no-streaming --check-seconds 0 --secondary ${SEC:-none} > $O/run.json 2> $O/run.err || { tail -5 $O/run.err; exit 1; }
+      --full --no-streaming --check-seconds 0 --secondary ${SEC:-none} > $O/run.json 2> $O/run.err || { tail -5 $O/run.err; exit 1; }
     python3 - "$O/run.json" "$k" "$r" <<'PY' | tee -a $O/knobs.txt
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One measurement call on the GPU box.  Steps (env, 1 = on): TESTS (all -m gpu tests + smoke),
-# BENCH (the driver's command: bench.py --gpus 1 --steps 20 --warmup 5), PROF (rocprofv3 kernel
+# BENCH (the complete line: bench.py --gpus 1 --steps 20 --warmup 5 --full), PROF (rocprofv3 kernel
 # stats of a short bench run), PMC (PMC passes of the streaming kernel on cfg2 / ns256 / cfg3),
 # CABI (C-ABI short-call tool).  TAG names the output dir gpurun_out/$TAG.  Every GPU step runs
 # under its own time limit and the script stops at the first failure.
@@ -13,7 +13,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   s=$?; echo "SMOKE_EXIT $s" >> $O/smoke.log; tail -1 $O/smoke.log; [ $s -eq 0 ] || exit $s
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 ${BENCH_TIMEOUT:-500} python3 bench.py --gpus 1 --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
+  timeout -k 10 ${BENCH_TIMEOUT:-500} python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
   s=$?; echo "BENCH_EXIT $s"; [ $s -eq 0 ] || { tail -20 $O/bench.err; exit $s; }
   python3 - "$O/bench.json" <<'EOF'
 import json, sys
@@ -35,7 +35,7 @@ if [ "${CABI:-0}" = 1 ]; then
   tail -n 3 $O/cabi_stereo.txt $O/cabi_256.txt
 fi
 if [ "${PROF:-1}" = 1 ]; then
-  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-pmc > $O/prof_bench.log 2>&1 )
+  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-pmc > $O/prof_bench.log 2>&1 )
   s=$?; echo "PROF_EXIT $s"; [ $s -eq 0 ] || exit $s
   f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -12 "$f"
 fi

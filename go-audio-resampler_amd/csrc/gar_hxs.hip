@@ -21,6 +21,10 @@ GAR_HXS_FOR_ALL(GAR_HXS_EXT)
 GAR_HXT_FOR_A(GAR_HXT_EXT)
 GAR_HXT_FOR_B(GAR_HXT_EXT)
 #undef GAR_HXT_EXT
+// lean-loader kernels: gar_hxt_i3.hip
+#define GAR_HXT_EXT_LEAN(NS, F, V, L, E) extern template hipError_t hxtLaunch<NS, F, V, L, E>(const HxsArgs&, size_t, int64_t, hipStream_t);
+GAR_HXT_FOR_LEAN(GAR_HXT_EXT_LEAN)
+#undef GAR_HXT_EXT_LEAN
 
 namespace {
 constexpr int kProfWords = 64 + 2 * 4096;
@@ -92,7 +96,9 @@ int64_t fdiv(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b)
 int64_t cdiv(int64_t a, int64_t b) { return -fdiv(-a, b); }
 
 template <int NS, int NL>
-hipError_t hxtFmtL(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st) {
+hipError_t hxtFmtL(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, bool lean) {
+    if constexpr (NS == kHxtLeanNS)
+        if (lean && x.fmt == 1 && x.vst == 2) return hxtLaunch<NS, 1, 2, NL, 1>(x, lds, blocks, st);
     if (x.fmt == 1 && x.vst == 2) return hxtLaunch<NS, 1, 2, NL>(x, lds, blocks, st);
     if (x.fmt == 2 && x.vst == 0) return hxtLaunch<NS, 2, 0, NL>(x, lds, blocks, st);
     if (x.fmt == 2 && x.vst == 1) return hxtLaunch<NS, 2, 1, NL>(x, lds, blocks, st);
@@ -100,20 +106,33 @@ hipError_t hxtFmtL(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st)
     return hipErrorNotSupported;
 }
 template <int NS>
-hipError_t hxtFmt(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st) {
-    return x.ncomp + 6 <= kHxtWaves ? hxtFmtL<NS, 6>(x, lds, blocks, st) : hxtFmtL<NS, 4>(x, lds, blocks, st);
+hipError_t hxtFmt(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, bool lean) {
+    return x.ncomp + 6 <= kHxtWaves ? hxtFmtL<NS, 6>(x, lds, blocks, st, lean) : hxtFmtL<NS, 4>(x, lds, blocks, st, lean);
+}
+
+// The launch's plan and ring are exactly the geometry the lean loaders (gar_hxt.hpp, HxtLeanGeo<NL>)
+// were compiled for.
+template <int NL>
+bool hxtLeanGeoIs(const HxsArgs& x) {
+    using Geo = HxtLeanGeo<NL>;
+    return x.Qc == Geo::Qc && x.G == Geo::G && x.R == Geo::R && x.Rt == Geo::Rt && x.Wg == Geo::Wg && x.mirror == Geo::mirror;
 }
 
 // Compute-wave roles of hxt_kernel for nprog row blocks (HxsArgs::role): the first 4*floor(nprog/4)
 // row blocks one wave each; one remaining row block shared by 4 waves (every 4th period), two by
 // 2 waves each (every 2nd period), so waves w, w+4, w+8 -- one SIMD -- carry equal MFMA work.
 // Returns the compute wave count; *maxStride the largest period stride.
-static int hxtRoles(int nprog, int NS, int* role, int* maxStride) {
-    // knob GAR_HXT_ROLES: 1 balanced, 0 one wave per row block; default balanced for NS >= 10 only
-    // (profiles/r04_ab: NS = 9 cfg2 0.125 ms one-per-row-block vs 0.145 balanced -- six loaders
-    // beside ten compute waves keep the ring ahead; NS = 10 cfg3 is the other way round)
-    static const int knobRoles = std::getenv("GAR_HXT_ROLES") ? std::atoi(std::getenv("GAR_HXT_ROLES")) : -1;
-    const bool balanced = knobRoles >= 0 ? knobRoles != 0 : NS >= 10;
+static int hxtRoles(int nprog, int NS, int* role, int* maxStride, bool leanPlan = false) {
+    // knob GAR_HXT_ROLES (read per launch, so one test process compares both): 1 balanced, 0 one wave per
+    // row block; default balanced for NS >= 10, and for the NS = 9 launches that run the lean loaders.
+    // r04 (profiles/r04_ab): NS = 9 cfg2 0.125 ms one-per-row-block vs 0.145 balanced -- four generic loaders
+    // beside twelve compute waves did not keep the ring ahead; NS = 10 cfg3 was the other way round.
+    // r07 (profiles/r07_ab_cfg2_roles.txt): with the lean loaders four are enough -- cfg2 0.112-0.120 ms
+    // balanced against 0.121-0.127 one-per-row-block and 0.123-0.129 for the r06 build on the same box.
+    // NS = 9 plans on the generic loaders (other geometries, 16- / 32-channel rows) keep one wave per row block.
+    const char* envRoles = std::getenv("GAR_HXT_ROLES");
+    const int knobRoles = envRoles ? std::atoi(envRoles) : -1;
+    const bool balanced = knobRoles >= 0 ? knobRoles != 0 : (NS >= 10 || leanPlan);
     int w = 0;
     *maxStride = 1;
     if (!balanced) {  // one wave per row block (hxs_kernel's mapping), six loaders beside ten compute waves
@@ -283,7 +302,16 @@ hipError_t launchHxs(const HxDev& p, const SrcDesc& src, const OutDesc& od, int 
     int role[kHxtMaxComp] = {}, maxStride = 1, ncomp = 0;
     bool hxt = knobHxt != 0 && !small && !od.pcm && !od.f64 && !src.in_pcm &&
                ((fmt == 1 && vst == 2) || (fmt == 2 && (vst == 0 || vst == 1)));
-    if (hxt) ncomp = hxtRoles(p.nw, p.NS, role, &maxStride);
+    // the launch can run the lean loaders (gar_hxt.hpp, round 7: the Q24 44.1k -> 48k plan on stereo f32
+    // frames; knob GAR_HXT_LEAN=0, read per launch so one test process compares both: generic loaders and
+    // their role default for this plan too) -- confirmed against the ring geometry below
+    bool leanPlan = hxt && !kHxsDev && p.NS == kHxtLeanNS && Pc == kHxtLeanPc && Qc == HxtLeanGeo<4>::Qc && p.Kread == 420 &&
+                    p.nw == 10 && fmt == 1 && vst == 2 && src.in_fs == 2 && inEsz == 4 && Np >= HxtLeanGeo<4>::G;
+    if (leanPlan) {
+        const char* e = std::getenv("GAR_HXT_LEAN");
+        leanPlan = !e || std::atoi(e) != 0;
+    }
+    if (hxt) ncomp = hxtRoles(p.nw, p.NS, role, &maxStride, leanPlan);
     wide = wide && hxt && fmt == 2 && vst == 0;
     if (wide) fmt = 5;
 
@@ -397,10 +425,12 @@ hipError_t launchHxs(const HxDev& p, const SrcDesc& src, const OutDesc& od, int 
     x.dftC = p.dftC;
     x.T1 = p.T1;
     x.T2 = p.T2;
+    // lean loaders: an exact match of the plan and ring fields; everything else runs the generic loaders
+    const bool lean = leanPlan && hxt && (ncomp + 6 <= kHxtWaves ? hxtLeanGeoIs<6>(x) : hxtLeanGeoIs<4>(x));
     if (trace)
-        fprintf(stderr, "%s: small=%d o[%lld,%lld) C=%d G=%d Np=%lld ngroups=%d nblocks=%d R=%d Rt=%d Wg=%d fmt=%d vst=%d fast[%lld,%lld)\n",
+        fprintf(stderr, "%s: small=%d o[%lld,%lld) C=%d G=%d Np=%lld ngroups=%d nblocks=%d R=%d Rt=%d Wg=%d fmt=%d vst=%d fast[%lld,%lld) ncomp=%d lean=%d\n",
                 hxt ? "hxt" : "hxs", x.small, (long long)od.o_lo, (long long)od.o_hi, C, G, (long long)Np, x.ngroups, x.nblocks, R, Rt, Wg, x.fmt, x.vst,
-                (long long)x.fastLo, (long long)x.fastHi);
+                (long long)x.fastLo, (long long)x.fastHi, ncomp, lean ? 1 : 0);
     if (hc && hc->n > 0 && hc->dst) {  // history keep folded into this launch (no gather_kernel after it)
         x.hdst = static_cast<float*>(hc->dst);
         x.ht0 = hc->t0;
@@ -453,7 +483,7 @@ hipError_t launchHxs(const HxDev& p, const SrcDesc& src, const OutDesc& od, int 
     if (hxt) {
         const int64_t hblocks = blocks;
         switch (p.NS) {
-#define GAR_HXT_NS(n) case n: return hxtFmt<n>(x, lds, hblocks, stream);
+#define GAR_HXT_NS(n) case n: return hxtFmt<n>(x, lds, hblocks, stream, lean);
 #if !GAR_HXS_QUICK
             GAR_HXT_NS(1) GAR_HXT_NS(2) GAR_HXT_NS(3) GAR_HXT_NS(4) GAR_HXT_NS(5) GAR_HXT_NS(6) GAR_HXT_NS(7)
             GAR_HXT_NS(8)

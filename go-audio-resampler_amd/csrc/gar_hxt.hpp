@@ -479,12 +479,13 @@ __device__ __forceinline__ void hxtCoopStage0(const HxsArgs& x, const HxsShared&
 
 template <int FMT, int NL>
 __device__ __forceinline__ void hxtLoaders(const HxsArgs& x, const HxsShared& sh, const HxtSync& sy, int b, int l,
-                                           int lane, int coop, unsigned long long* waited) {
+                                           int lane, int coop, unsigned long long* waited, int jStop = INT_MAX) {
     if constexpr (GAR_HXT_LPRIO > 0) __builtin_amdgcn_s_setprio(GAR_HXT_LPRIO);
     const HxsArgsP xp = hxsCold();
     const int GQ = x.G * x.Qc, Wg = x.Wg, R = x.R;
-    const int P = (Wg + GQ - 1) / GQ, nL = P + x.ngroups - 1;
-    const int nstepsPad = hxsStepsPad(x);
+    // jStop (lean kernels, round 7): only loads / steps j < jStop (jStop even) -- the lean loaders take over there
+    const int P = (Wg + GQ - 1) / GQ, nL = min(P + x.ngroups - 1, jStop);
+    const int nstepsPad = min(hxsStepsPad(x), jStop);
     const int dbg = kHxsDev ? x.dbg : GAR_HXT_CTDBG;
     // per block (uniform): loads go through the buffer records ("fast") when every column of the
     // block is live and the load's first row lies at or after the raw input's first row
@@ -560,6 +561,210 @@ __device__ __forceinline__ void hxtLoaders(const HxsArgs& x, const HxsShared& sh
     }
 }
 
+// ---- lean loaders (round 7) ------------------------------------------------------------------
+// The generic loader step recomputes every item's global offset, live mask, ring row, wrap and mirror
+// condition per step (kept opaque on purpose: hoisted, they spill), ~2x the instructions of the split
+// itself.  For one plan geometry known at compile time (stereo f32 frames, Qc / G / Kread fixed, hence
+// GQ, Wg, R, Rt, the ring's slot count) none of that depends on the step:
+//  * loads j >= P land in ring slot (j - P) % nslot, so the step loop is unrolled over the slots (times
+//    the kHxtD register buffers) and every body's ring rows are constants;
+//  * only slot nslot - 2 crosses the ring's end, and the rows that wrap are exactly the mirrored head:
+//    every row is written at its unwrapped ring row p0 + row (< R + mirror), the wrapping rows once
+//    more at p0 + row - R -- the same image as hxtConvert's wrap + mirror copy;
+//  * items are dealt so that an item's quad and piece are a per-loader part (folded once per block
+//    into the lane's ring address and buffer offset) plus a constant: every ring write is base +
+//    immediate, every load one v_add of a per-chunk scalar.
+// Same loads, same split, same loud test (running max, exact re-gather when it fires), same ring
+// image: the compute waves and the bits do not change.  Loads before the steady state (history
+// seam, stream start) stay with hxtLoaders, which stops at the step the lean loop starts from.
+template <int QC, int G_, int KREAD>
+struct HxtGeo {  // hxsRingFor's geometry (gar_hxs.hip) as constants; the launcher dispatches on an exact match
+    static constexpr int Qc = QC, G = G_, GQ = G_ * QC, Wg = (G_ - 1) * QC + KREAD;
+    static constexpr int nslot = (Wg + GQ + GQ - 1) / GQ, R = nslot * GQ;
+    static constexpr int mirror = Wg > GQ ? Wg - GQ : 0;
+    static constexpr int Rt = (R + mirror + 15) / 16 * 16;
+    static constexpr int P = (Wg + GQ - 1) / GQ;
+    static constexpr uint32_t QS = 16u * Rt + 64u, dL = 8u * Rt;
+    // first step (j - P) whose ring rows had an occupant, hxtFreeNeed: step i waits for group i - i0
+    static constexpr int i0 = (R + 1 - Wg + GQ - 1) / GQ - 1;
+    static_assert(Wg > GQ && mirror < GQ && P % kHxtD == 0 && i0 >= 0, "lean loaders: ring shape");
+};
+// Q24 44.1k -> 48k (Qc 147, Kread 420): G = 5 beside six loaders, G = 4 beside four (balanced roles)
+template <int NL>
+using HxtLeanGeo = HxtGeo<147, NL >= 6 ? 5 : 4, 420>;
+constexpr int kHxtLeanPc = 160, kHxtLeanNS = 9;
+
+// Item k of loader l: quad qL(l) + q(k), 64-row piece pcL(l) + pcS(k).
+template <int NL>
+struct HxtLeanMap;
+template <>
+struct HxtLeanMap<6> {  // loader l: pieces l, l + 6 of every quad
+    static constexpr int kItems = 8, kMaxPcL = 5;
+    __host__ __device__ static constexpr int q(int k) { return k & 3; }
+    __host__ __device__ static constexpr int pcS(int k) { return 6 * (k >> 2); }
+    __device__ static int qL(int) { return 0; }
+    __device__ static int pcL(int l) { return l; }
+};
+template <>
+struct HxtLeanMap<4> {  // loader l: quad l, every piece
+    static constexpr int kItems = 10, kMaxPcL = 0;
+    __host__ __device__ static constexpr int q(int) { return 0; }
+    __host__ __device__ static constexpr int pcS(int k) { return k; }
+    __device__ static int qL(int l) { return l; }
+    __device__ static int pcL(int) { return 0; }
+};
+
+typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) u32x2v lds_u2;
+__device__ __forceinline__ void hxtLdsPut(uint32_t a, uint2 v) { *reinterpret_cast<lds_u2*>(a) = u32x2v{v.x, v.y}; }
+
+// hxtLoudLoad with the lean item mapping (rare: a loud element in the load at column row T0).
+template <int NL, class Geo>
+__device__ GAR_HXT_SLOW_ATTR void hxtLoudLoadLean(HxsArgsP xp, int T0, int b, int l, int lane, HxsShared sh) {
+    using M = HxtLeanMap<NL>;
+    const SrcDesc src = kload(&xp->src);
+    HxsStage st;
+    st.T0 = T0;
+    st.nrow = Geo::GQ;
+    st.fast = true;
+    const int p0 = uni(T0 % xp->R);
+    for (int k = 0; k < M::kItems; ++k) {
+        const int row = 64 * (M::pcL(l) + M::pcS(k)) + lane, q = M::qL(l) + M::q(k);
+        if (row >= Geo::GQ) continue;
+        f32x4 e;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const int col = b * 16 + 4 * q + n;
+            const int kk = col / xp->C, c = col - kk * xp->C;
+            e[n] = hxsGather(src, hxsChunkRow(xp, kk, T0 + row), c, xp->A);
+        }
+        hxsPutItem(xp, st, p0, q, row, e, sh.ring, sh.QS, sh.loudLo, sh.loudHi, sh.flag);
+    }
+}
+
+// Issue one load: the loader's items at buffer offset v0 (+ chunk and piece constants); a dead load's
+// v0 lies past the records (zeros, no memory access: the same instruction pattern on every path).
+template <int NL>
+__device__ __forceinline__ void hxtIssueLean(const HxsRegSrc& rs, uint32_t v0, uint32_t chunkB, HxtBuf<1, NL>& r) {
+    using M = HxtLeanMap<NL>;
+#pragma unroll
+    for (int k = 0; k < M::kItems; ++k) {
+        const uint32_t o = v0 + 2u * M::q(k) * chunkB + 512u * M::pcS(k);
+        r.a[k] = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rs.r, static_cast<int>(o), 0, 0));
+        r.b[k] = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rs.r, static_cast<int>(o + chunkB), 0, 0));
+    }
+}
+
+// One load -> ring slot `slot` (a constant after unrolling).  rb: LDS address of the lane's row 0 of
+// quad qL (ring + qL QS + 8 laneRow); laneRow = 64 pcL + lane.  Returns the load's running loud max.
+template <int NL, class Geo>
+__device__ __forceinline__ uint32_t hxtConvertLean(const HxtBuf<1, NL>& r, int slot, uint32_t rb, int laneRow) {
+    using M = HxtLeanMap<NL>;
+    constexpr int K = M::kItems, GQ = Geo::GQ, R = Geo::R, kMaxLaneRow = 64 * M::kMaxPcL + 63, kSplitChunk = 4;
+    const int p0 = (Geo::mirror + (slot + 1) * GQ) % R;  // (Wg + slot GQ) % R
+    uint32_t m = 0;
+#pragma unroll
+    for (int k0 = 0; k0 < K; k0 += kSplitChunk) {
+        uint2 hv[kSplitChunk], lv[kSplitChunk];
+#pragma unroll
+        for (int u = 0; u < kSplitChunk; ++u) {
+            if (k0 + u >= K) break;
+            const f32x4 e = hxtItem<1, NL>(r, k0 + u);
+            m = max(m, max(max(hxtMag(e[0]), hxtMag(e[1])), max(hxtMag(e[2]), hxtMag(e[3]))));
+            hxSplit2(e[0], e[1], hv[u].x, lv[u].x);
+            hxSplit2(e[2], e[3], hv[u].y, lv[u].y);
+        }
+#pragma unroll
+        for (int u = 0; u < kSplitChunk; ++u) {
+            if (k0 + u >= K) break;
+            const int rowS = 64 * M::pcS(k0 + u);  // the item's first row of the loader's piece 0
+            const int pu = p0 + rowS;               // unwrapped ring row of laneRow 0
+            const int wrapAt = R - pu;              // lane rows >= wrapAt lie past the ring's end
+            const uint32_t a = rb + static_cast<uint32_t>(M::q(k0 + u)) * Geo::QS + 8u * static_cast<uint32_t>(pu);
+            if (rowS + kMaxLaneRow < GQ || laneRow < GQ - rowS) {  // rows of this load (the last piece is partial)
+                hxtLdsPut(a, hv[u]);            // p0 + row < R + mirror: in place, or the mirror copy of a wrapped row
+                hxtLdsPut(a + Geo::dL, lv[u]);
+                if (wrapAt <= kMaxLaneRow && laneRow >= wrapAt) {  // wrapped rows (slot nslot - 2 only): the ring's head
+                    hxtLdsPut(a - 8u * R, hv[u]);
+                    hxtLdsPut(a - 8u * R + Geo::dL, lv[u]);
+                }
+            }
+        }
+    }
+    return m;
+}
+
+// First step the lean loop may start from in block b: the first j >= P, a multiple of the unrolled
+// body past P, from which every load comes through the buffer records; INT_MAX when none does.
+template <class Geo>
+__device__ __forceinline__ int hxtLeanFrom(const HxsArgs& x, int b, int kU) {
+    const bool blockLive = b * 16 + 15 < x.ncols && x.fastHi > x.fastLo;
+    if (!blockLive) return INT_MAX;
+    const int64_t row0 = (x.a_lo + static_cast<int64_t>((b * 16) / x.C) * x.Np) * Geo::Qc;
+    const int64_t lack = x.fastLo - (row0 + Geo::Wg);  // rows load P starts before the raw input
+    const int64_t i = lack <= 0 ? 0 : (lack + Geo::GQ - 1) / Geo::GQ;
+    const int64_t iu = (i + kU - 1) / kU * kU;
+    return iu > (1 << 28) ? INT_MAX : Geo::P + static_cast<int>(iu);
+}
+
+// Loader wave l from step jBegin (= P after a cooperative fill, whose barriers it meets like
+// hxtLoaders; else the step hxtLoaders stopped before, nothing in flight).
+template <int NL, class Geo>
+__device__ __forceinline__ void hxtLoadersLean(const HxsArgs& x, const HxsShared& sh, const HxtSync& sy, int b, int l,
+                                               int lane, int coop, int jBegin, unsigned long long* waited) {
+    using M = HxtLeanMap<NL>;
+    static_assert(M::kItems == hxtItems<NL>() && 64 * (M::kMaxPcL + 1 + M::pcS(M::kItems - 1)) >= Geo::GQ, "lean items cover a load");
+    static_assert(kHxtD == 2, "two register buffers");
+    constexpr int GQ = Geo::GQ, P = Geo::P, kU = (Geo::nslot % 2 ? 2 : 1) * Geo::nslot;  // slots x buffers
+    if constexpr (GAR_HXT_LPRIO > 0) __builtin_amdgcn_s_setprio(GAR_HXT_LPRIO);
+    const HxsArgsP xp = hxsCold();
+    const int nL = P + x.ngroups - 1;
+    const int dbg = kHxsDev ? x.dbg : GAR_HXT_CTDBG;
+    const HxsRegSrc rs = hxsRegSrc<1>(xp, b, lane);  // stereo f32 frames: 8-B rows
+    const uint32_t chunkB = static_cast<uint32_t>(rs.chunkB);
+    const int laneRow = 64 * M::pcL(l) + lane;
+    const uint32_t rb = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_s4p)(sh.ring))) +
+                        static_cast<uint32_t>(M::qL(l)) * Geo::QS + 8u * static_cast<uint32_t>(laneRow);
+    // buffer offset of the lane's row of load j (chunk 2 qL), advanced per issue
+    uint32_t vo = 8u * static_cast<uint32_t>(laneRow) + 2u * static_cast<uint32_t>(M::qL(l)) * chunkB +
+                  8u * static_cast<uint32_t>(Geo::Wg + (jBegin - P) * GQ);
+    int jI = jBegin;
+    HxtBuf<1, NL> buf[kHxtD];
+    auto issue = [&](HxtBuf<1, NL>& r) {
+        const bool live = jI < nL && !(dbg & 1);
+        hxtIssueLean<NL>(rs, live ? vo : 0x80000000u, chunkB, r);
+        vo += 8u * GQ;
+        ++jI;
+    };
+    if (coop == 2) {  // ordered fill (hxtLoaders): load P after the compute waves' first batch, P + 1 after the window
+        hxsBarrier();
+        issue(buf[0]);
+        hxsBarrier();
+        issue(buf[1]);
+    } else {
+        issue(buf[0]);
+        issue(buf[1]);
+        if (coop) hxsBarrier();
+    }
+    for (int j0 = jBegin; j0 < nL; j0 += kU) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int j = j0 + u;
+            if (j < nL) {
+                const int need = j - P - Geo::i0 + 1;  // hxtFreeNeed(j): groups 0 .. need - 1 read the rows this load overwrites
+                if (need > 0 && !(dbg & 64)) hxtWait(x, sy, sy.cpArr, need - 1, x.ncomp, kHxtErrSlotWait, lane, waited);
+                if (!(dbg & 16)) {
+                    const uint32_t m = hxtConvertLean<NL, Geo>(buf[u % kHxtD], u % Geo::nslot, rb, laneRow);
+                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(m >= kHxtLoudBits) != 0, 0))
+                        hxtLoudLoadLean<NL, Geo>(xp, Geo::Wg + (j - P) * GQ, b, l, lane, sh);
+                }
+                hxtArrive(sy.ldArr, j, lane);
+            }
+            issue(buf[u % kHxtD]);
+        }
+    }
+}
+
 // Workgroup slot -> block.  x.xcdPair 2 (FMT 5): chunk-major -- slot i runs block (i % 8) * (nblocks / 8) +
 // i / 8, so every channel group of a few consecutive chunks runs on one XCD (the dispatcher deals slots
 // round-robin over the 8 XCDs) and the 1-KB rows of those chunks are read and written together.
@@ -609,6 +814,7 @@ __device__ __forceinline__ void hxtGroups(const HxsArgs& x, const HxsShared& sh_
         const f32x4 y = hxScale(oA, oL, sh);
         if (dbg & 2) return;
         if constexpr (FAST && VST == 2 && GAR_HXT_NTST2) {
+            static_assert(NT == 1, "stereo frame-pair stores: one tile per period");
             hxtStoreStereoNt(obase + static_cast<int64_t>(p) * pstride, y, lane);
         } else if constexpr (FAST) {
             hxsStoreFast<VST>(x, obase + static_cast<int64_t>(p) * pstride + h * tileOut, y, lane);
@@ -745,7 +951,8 @@ __device__ __forceinline__ void hxtCompute(const HxsArgs& x, const HxsShared& sh
 
 // FMT: 1 stereo f32 frames, 2 rows of 16 f32 channels.  VST: 0 any f32 layout, 1 channel-contiguous
 // f32, 2 stereo-interleaved f32 (hxsStoreFast).
-template <int NS, int FMT, int VST, int NL>
+// LEAN 1: the lean loaders' geometry (HxtLeanGeo<NL>, stereo frames), checked by the launcher.
+template <int NS, int FMT, int VST, int NL, int LEAN = 0>
 __global__ __launch_bounds__(64 * kHxtWaves) void hxt_kernel(HxsArgs x) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     HxsShared s;
@@ -788,7 +995,14 @@ __global__ __launch_bounds__(64 * kHxtWaves) void hxt_kernel(HxsArgs x) {
         const bool first = bi == static_cast<int>(blockIdx.x);
         unsigned long long* stp = (stampW && first) ? st : nullptr;
         if (comp) hxtCompute<NS, VST, FMT>(x, s, sy, b, wt, lane, NL, coop, stp);
-        else hxtLoaders<FMT, NL>(x, s, sy, b, wt - x.ncomp, lane, coop, stp);
+        else if constexpr (LEAN != 0) {
+            static_assert(FMT == 1, "lean loaders: stereo f32 frames");
+            using Geo = HxtLeanGeo<NL>;
+            constexpr int kU = (Geo::nslot % 2 ? 2 : 1) * Geo::nslot;
+            const int jLean = coop ? Geo::P : hxtLeanFrom<Geo>(x, b, kU);  // uniform
+            if (!coop) hxtLoaders<FMT, NL>(x, s, sy, b, wt - x.ncomp, lane, 0, stp, jLean);
+            if (jLean != INT_MAX) hxtLoadersLean<NL, Geo>(x, s, sy, b, wt - x.ncomp, lane, coop, jLean, stp);
+        } else hxtLoaders<FMT, NL>(x, s, sy, b, wt - x.ncomp, lane, coop, stp);
         if (stampW && first) tBlockEnd = __builtin_amdgcn_s_memtime();
         __syncthreads();  // every wave's part of the block done; flag final
         if (*s.flag) {  // uniform
@@ -829,11 +1043,11 @@ __global__ __launch_bounds__(64 * kHxtWaves) void hxt_kernel(HxsArgs x) {
     }
 }
 
-template <int NS, int FMT, int VST, int NL>
+template <int NS, int FMT, int VST, int NL, int LEAN = 0>
 hipError_t hxtLaunch(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st) {
     if (x.ncomp + NL > kHxtWaves) return hipErrorInvalidConfiguration;
-    if (const size_t lim_ = setMaxLdsOnce(reinterpret_cast<const void*>(&hxt_kernel<NS, FMT, VST, NL>)); lim_ < lds) return ldsTooBig("hxt_kernel", lds, lim_);
-    hipLaunchKernelGGL((hxt_kernel<NS, FMT, VST, NL>), dim3(static_cast<unsigned>(blocks)), dim3(64 * (x.ncomp + NL)), lds,
+    if (const size_t lim_ = setMaxLdsOnce(reinterpret_cast<const void*>(&hxt_kernel<NS, FMT, VST, NL, LEAN>)); lim_ < lds) return ldsTooBig("hxt_kernel", lds, lim_);
+    hipLaunchKernelGGL((hxt_kernel<NS, FMT, VST, NL, LEAN>), dim3(static_cast<unsigned>(blocks)), dim3(64 * (x.ncomp + NL)), lds,
                        st, x);
     return hipGetLastError();
 }
@@ -849,5 +1063,8 @@ hipError_t hxtLaunch(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t s
 #define GAR_HXT_FOR_B(M) GAR_HXT_FOR3(M, 8) GAR_HXT_FOR3(M, 9) GAR_HXT_FOR3(M, 10)
 #endif
 #define GAR_HXT_INST(NS, F, V, L) template hipError_t hxtLaunch<NS, F, V, L>(const HxsArgs&, size_t, int64_t, hipStream_t);
+// lean-loader kernels (gar_hxt_i3.hip): NS 9, stereo frames in and out, six / four loaders
+#define GAR_HXT_FOR_LEAN(M) M(kHxtLeanNS, 1, 2, 6, 1) M(kHxtLeanNS, 1, 2, 4, 1)
+#define GAR_HXT_INST_LEAN(NS, F, V, L, E) template hipError_t hxtLaunch<NS, F, V, L, E>(const HxsArgs&, size_t, int64_t, hipStream_t);
 
 }  // namespace gar

@@ -157,7 +157,7 @@ bool attachHx(const FirPeriodic& f, StageRT::HxRT& h, BgDev& bg, bool dry, const
             d.dftC = static_cast<const double*>(h.banks2.p);
         }
     }
-    d.hxsOk = hxsPlanFits(d) ? 1 : 0;  // PCM stores/loads fuse only into hxs_kernel (pcmFusable)
+    d.hxsOk = hxsPlanFits(d) ? 1 : 0;  // PCM / half stores and loads fuse only into hxs_kernel (pcmFusable)
     bg.hx = &h.d;
     return true;
 }
@@ -445,7 +445,7 @@ struct InView {
     const void* p = nullptr;
     int64_t fs = 0, cs = 0;
     int f64 = 0;
-    int pcm = 0;  // integer PCM input bits (fused into hxs_kernel's loads; gar_process_device only)
+    int pcm = 0;  // integer PCM input bits, or GAR_F16 / GAR_BF16 (fused into hxs_kernel's loads; gar_process_device only)
     int64_t n = 0;
     bool zeros = false;
 };
@@ -454,7 +454,7 @@ struct OutView {
     void* p = nullptr;
     int64_t fs = 0, cs = 0;
     int f64 = 0;
-    int pcm = 0;  // integer PCM output bits (fused into hxs_kernel's stores)
+    int pcm = 0;  // integer PCM output bits, or GAR_F16 / GAR_BF16 (fused into hxs_kernel's stores)
 };
 
 // Pinned host buffer the device reads in place (CubicStage checkpoints); reused only
@@ -1273,6 +1273,8 @@ gar_status validate(const gar_config* c) {
         return guard(GAR_ERR_INVALID_CONFIG, "invalid resampler configuration: sample rates must be positive");
     if (c->channels < 1) return guard(GAR_ERR_INVALID_CONFIG, "invalid resampler configuration: channels must be at least 1");
     if (c->channels > 256) return guard(GAR_ERR_INVALID_CONFIG, "invalid resampler configuration: too many channels (max 256)");
+    if (c->compute_dtype == GAR_F16 || c->compute_dtype == GAR_BF16)
+        return guard(GAR_ERR_INVALID_CONFIG, "invalid resampler configuration: f16 / bf16 are sample types of the device entry points, not compute types");
     const double r = c->output_rate / c->input_rate;
     if (r < 1.0 / 256.0 || r > 256.0)
         return guard(GAR_ERR_INVALID_CONFIG, "invalid resampler configuration: resampling ratio out of range");
@@ -1531,8 +1533,12 @@ gar_status monoCall(Handle* h, int ch, const T* in, int64_t n, T* out, int64_t c
 namespace gar {
 namespace {
 bool isPcm(int32_t t) { return t == GAR_PCM16 || t == GAR_PCM24 || t == GAR_PCM32; }
-bool ioTypeOk(int32_t t) { return t == GAR_F64 || t == GAR_F32 || t == GAR_F32_EXACT || isPcm(t); }
-// PCM conversion fused into hxs_kernel's loads and stores: one fused split-f16 stage streaming
+bool isHalf(int32_t t) { return t == GAR_F16 || t == GAR_BF16; }
+// sample types converted at the device entry points: integer PCM and f16 / bf16 (InView::pcm / OutView::pcm
+// carry the ABI code, which is also launchConvert's code for them)
+bool isNarrow(int32_t t) { return isPcm(t) || isHalf(t); }
+bool ioTypeOk(int32_t t) { return t == GAR_F64 || t == GAR_F32 || t == GAR_F32_EXACT || isNarrow(t); }
+// PCM / half conversion fused into hxs_kernel's loads and stores: one fused split-f16 stage streaming
 // through the row-block kernel (launchHxs's geometry); anything else stages the conversion.
 bool pcmFusable(const Handle* h) {
     if (h->dry || h->f64 || !h->hx || h->stages.size() != 1 || h->groups.size() != 1) return false;
@@ -1867,11 +1873,11 @@ gar_status gar_process_device(gar_resampler* r, const void* in, int32_t in_dtype
         iv.fs = in_fs;
         iv.cs = in_cs;
         iv.n = frames;
-        if (isPcm(in_dtype)) {
+        if (isNarrow(in_dtype)) {
             iv.f64 = 0;
             if (fuse) {
                 iv.pcm = in_dtype;
-            } else if (!r->dry) {  // staged: PCM -> compute dtype, then the ordinary path
+            } else if (!r->dry) {  // staged: PCM / half -> compute dtype, then the ordinary path
                 const int cf = r->f64 ? 1 : 0;
                 r->inStage.ensure(static_cast<size_t>(std::max<int64_t>(frames, 1)) * r->channels * (cf ? 8 : 4));
                 HIPCHK(launchConvert(in, in_dtype, in_fs, in_cs, r->inStage.p, cf, r->channels, 1, frames, r->channels, s));
@@ -1886,8 +1892,8 @@ gar_status gar_process_device(gar_resampler* r, const void* in, int32_t in_dtype
         ov.f64 = out_dtype == GAR_F64 ? 1 : 0;
         ov.fs = out_fs;
         ov.cs = out_cs;
-        const bool stageOut = isPcm(out_dtype) && !fuse && !r->dry;
-        if (isPcm(out_dtype)) {
+        const bool stageOut = isNarrow(out_dtype) && !fuse && !r->dry;
+        if (isNarrow(out_dtype)) {
             ov.f64 = 0;
             if (fuse) ov.pcm = out_dtype;
         }
@@ -1929,8 +1935,8 @@ gar_status gar_flush_device(gar_resampler* r, int32_t channels, void* out, int32
         ov.f64 = out_dtype == GAR_F64 ? 1 : 0;
         ov.fs = out_fs;
         ov.cs = out_cs;
-        const bool stageOut = isPcm(out_dtype) && !fuse && !r->dry;
-        if (isPcm(out_dtype)) {
+        const bool stageOut = isNarrow(out_dtype) && !fuse && !r->dry;
+        if (isNarrow(out_dtype)) {
             ov.f64 = 0;
             if (fuse) ov.pcm = out_dtype;
         }
@@ -2088,6 +2094,18 @@ const char* gar_last_error(void) { return g_err.c_str(); }
 void gar_profile_enable(gar_resampler* r, int32_t on) {
     if (!r) return;
     r->profile = on != 0;
+}
+
+gar_status gar_dev_half_convert(int32_t half_type, const double* in, int64_t n, uint16_t* from_f64, uint16_t* from_f32,
+                                float* widened) {
+    if (!isHalf(half_type) || n < 0 || (n > 0 && !in)) return guard(GAR_ERR_INVALID_ARGUMENT, "bad half conversion arguments");
+    for (int64_t i = 0; i < n; ++i) {
+        const uint16_t b = halfOfF64(in[i], half_type);
+        if (from_f64) from_f64[i] = b;
+        if (from_f32) from_f32[i] = halfOfF32(static_cast<float>(in[i]), half_type);
+        if (widened) widened[i] = halfToF32(b, half_type);
+    }
+    return GAR_OK;
 }
 
 int64_t gar_dev_pool_selftest(int32_t threads, int32_t iters, int32_t channels, int64_t frames) {

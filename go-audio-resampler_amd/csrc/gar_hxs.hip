@@ -12,7 +12,7 @@
 
 namespace gar {
 
-// instantiations live in gar_hxs_i1.hip / gar_hxs_i2.hip (compiled in parallel)
+// instantiations live in gar_hxs_i1.hip / gar_hxs_i2.hip / gar_hxs_i3.hip (compiled in parallel)
 #define GAR_HXS_EXT(NS, V) extern template hipError_t hxsLaunch<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t);
 GAR_HXS_FOR_ALL(GAR_HXS_EXT)
 #undef GAR_HXS_EXT
@@ -160,6 +160,7 @@ hipError_t hxsVst(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st) 
         case 1: return hxsLaunch<NS, 1>(x, lds, blocks, st);
         case 2: return hxsLaunch<NS, 2>(x, lds, blocks, st);
         case 4: return hxsLaunch<NS, 4>(x, lds, blocks, st);
+        case 5: return hxsLaunch<NS, 5>(x, lds, blocks, st);
         default: return hxsLaunch<NS, 3>(x, lds, blocks, st);
     }
 }
@@ -272,6 +273,9 @@ hipError_t launchHxs(const HxDev& p, const SrcDesc& src, const OutDesc& od, int 
         const uintptr_t hA = reinterpret_cast<uintptr_t>(src.hist);
         if (C == 2 && src.hist_ld == 2 && (hA & 7) == 0) fmt = 1;
         else if (C % 16 == 0 && src.hist_ld % 4 == 0 && (hA & 15) == 0) fmt = 2;
+    } else if (sampIsHalf(src.in_pcm)) {  // f16 / bf16: stereo frames (one dword each) or 16-channel rows (32 B)
+        if ((inA & 3) == 0 && stereoIl) fmt = 6;
+        else if ((inA & 7) == 0 && C % 16 == 0 && src.in_cs == 1 && src.in_fs % 4 == 0) fmt = 7;
     } else if (src.in_pcm == 16) {  // PCM16 / PCM24-32 stereo frames; other PCM layouts are gathered
         if ((inA & 3) == 0 && stereoIl) fmt = 3;
     } else if (src.in_pcm) {
@@ -288,7 +292,11 @@ hipError_t launchHxs(const HxDev& p, const SrcDesc& src, const OutDesc& od, int 
     const bool al = (reinterpret_cast<uintptr_t>(outBase) & 15) == 0;
     int vst;
     if (od.pcm == 16 && al && C == 2 && od.fs == 2 && od.cs == 1 && Pc % 4 == 0) vst = 4;  // int16 stereo frame pairs
-    else if (od.pcm) vst = 0;  // other PCM stores: the epilogue's checked per-element path
+    // half stereo frame pairs: 8-B stores at multiples of 8 B from the base, so an 8-B aligned base does (a flush
+    // after an odd number of output frame pairs has one)
+    else if (sampIsHalf(od.pcm) && (reinterpret_cast<uintptr_t>(outBase) & 7) == 0 && C == 2 && od.fs == 2 && od.cs == 1 &&
+             Pc % 4 == 0) vst = 5;
+    else if (od.pcm) vst = 0;  // other PCM / half stores: the epilogue's checked per-element path
     else if (od.f64) vst = 3;
     else if (al && C == 2 && od.fs == 2 && od.cs == 1 && Pc % 4 == 0) vst = 2;
     else if (al && od.fs == 1 && (od.cs * 4) % 16 == 0 && Pc % 4 == 0) vst = 1;
@@ -297,7 +305,7 @@ hipError_t launchHxs(const HxDev& p, const SrcDesc& src, const OutDesc& od, int 
     // balanced kernel (hxt_kernel): f32 stereo frames or 16-channel rows in, f32 out (knob GAR_HXT=0: hxs_kernel)
     // Default (knob unset): hxt_kernel wherever its load / store layouts apply -- after its loader spill
     // fixes it beats hxs_kernel on every BASELINE plan (profiles/r04_ab: cfg2 0.125 vs 0.130 ms, ns256
-    // 1.81 vs 1.84 ms, cfg3 0.33 vs 0.46 ms); hxs_kernel keeps PCM, f64 and other layouts.
+    // 1.81 vs 1.84 ms, cfg3 0.33 vs 0.46 ms); hxs_kernel keeps PCM, f16 / bf16, f64 and other layouts.
     static const int knobHxt = std::getenv("GAR_HXT") ? std::atoi(std::getenv("GAR_HXT")) : -1;
     int role[kHxtMaxComp] = {}, maxStride = 1, ncomp = 0;
     bool hxt = knobHxt != 0 && !small && !od.pcm && !od.f64 && !src.in_pcm &&

@@ -74,15 +74,17 @@ struct HxsArgs {
                            // 4 no MFMA, 16 no steady conversion
     int small;             // one period per column, window staged in one pass (hxsSmallStage)
     int bigSmall;          // development (GAR_HXS_SMALLK=0): small launches on hxs_kernel instead of hxs_small_kernel
-    int vst, fmt;          // epilogue layout (template VST), load layout 0 gathered / 1 STEREO / 2 ROW16
+    int vst, fmt;          // epilogue layout (template VST), load layout 0 gathered / 1 STEREO / 2 ROW16 /
+                           // 3, 4 STEREO PCM / 6 STEREO half / 7 ROW16 half (5: hxt_kernel's ROW32)
     int xcdPair;           // ROW16 blocks 2m, 2m+1 share every 128-B input/output line: run them on one XCD
     int nt;                // development: non-temporal output stores (GAR_HXS_NT)
     int64_t a_lo, a_hi;    // absolute macro periods of the launch
     int64_t o_lo, o_hi;    // outputs written
     const char* in;        // input element (t, c) at byte in + (t*in_fs + c*in_cs)*in_esz, t absolute, raw loads for t in [fastLo, fastHi)
     int64_t in_fs, in_cs, fastLo, fastHi;
-    int in_esz, in_pcm;    // bytes per input element; PCM bits (0: float input)
-    int out_pcm;           // PCM output bits (0: float output; stores go through the checked path)
+    int in_esz, in_pcm;    // bytes per input element; PCM bits or 4 / 5 for f16 / bf16 (0: f32 / f64 input)
+    int out_pcm;           // PCM output bits or 4 / 5 for f16 / bf16 (0: f32 / f64 output); stores go through
+                           // the checked path unless VST is the type's frame-pair layout (4, 5)
     float* hdst;           // folded history keep (HistCopy): hdst[(t - ht0) * C + c] = src(t, c), t < ht0 + hn
     int64_t ht0, hn;
     char* out;             // output (o, c) at out + o*out_fs + c*out_cs (bytes), o absolute
@@ -208,6 +210,10 @@ __device__ __forceinline__ void hxsFixup(HxsArgsP xp, int b, const int* loudLo, 
 //    one buffer_load_dwordx2 per chunk (64 lanes = 512 B contiguous);
 //  * ROW16 (fmt 2, C % 16 == 0, 16-B aligned rows): quad q = channels 4q..4q+3 of the block's
 //    chunk, one buffer_load_dwordx4;
+//  * STEREO half (fmt 6, f16 / bf16 frames): as STEREO PCM16 (fmt 3), one buffer_load_dword per
+//    chunk row (both channels), widened to two f32 at conversion time;
+//  * ROW16 half (fmt 7, C % 16 == 0, 8-B aligned 2-byte rows): quad q = channels 4q..4q+3, one
+//    buffer_load_dwordx2 (a 16-row piece is 16 whole 32-B block rows);
 //  * every other layout, f64 input and the edges (rows before the input: history seam, stream
 //    start; partial blocks): gathered at conversion time.
 // Rows past the caller's input read zeros through the buffer records.
@@ -250,7 +256,7 @@ __device__ __forceinline__ float hxsGather(const SrcDesc& s, int64_t t, int c, c
     const bool inH = valid && s.hist && h >= 0 && h < s.hist_len;
     const bool inI = valid && !inH && s.in && i >= 0 && i < s.in_len;
     const float* hp = static_cast<const float*>(s.hist) + (inH ? h * s.hist_ld + c : 0);
-    if (s.in_pcm) {  // integer PCM input (main.go:444-472 scaling)
+    if (s.in_pcm) {  // integer PCM input (main.go:444-472 scaling) or f16 / bf16 (exact widening)
         const int64_t e = inI ? i * s.in_fs + static_cast<int64_t>(c) * s.in_cs : 0;
         const float vh = *(inH ? hp : static_cast<const float*>(dummy));
         const float vi = inI ? static_cast<float>(pcmRead(s.in, e, s.in_pcm)) : 0.f;
@@ -281,7 +287,7 @@ __device__ __forceinline__ HxsStage hxsStage(XP x, int b, int T0, int nrow) {
     s.nrow = nrow;
     const int c0 = b * 16, c1 = c0 + 15;
     const int64_t tlo = (x->a_lo + static_cast<int64_t>(c0 / x->C) * x->Np) * x->Qc + T0;
-    s.fast = x->fmt >= 1 && x->fmt <= 4 && c1 < x->ncols && tlo >= x->fastLo && x->fastHi > x->fastLo;
+    s.fast = ((x->fmt >= 1 && x->fmt <= 4) || x->fmt == 6 || x->fmt == 7) && c1 < x->ncols && tlo >= x->fastLo && x->fastHi > x->fastLo;
     return s;
 }
 // Load j of a block: j < P = ceil(Wg / GQ) the parts of stage 0 (rows [j*GQ, ...) up to Wg),
@@ -374,6 +380,22 @@ template <>
 struct HxsRegBuf<3> {  // STEREO PCM16: one dword (both channels) per chunk row
     uint32_t a[kHxsItems], b[kHxsItems];
 };
+template <>
+struct HxsRegBuf<6> {  // STEREO f16 / bf16: one dword (both channels) per chunk row
+    uint32_t a[kHxsItems], b[kHxsItems];
+};
+template <>
+struct HxsRegBuf<7> {  // ROW16 f16 / bf16: four channels (8 B) per lane
+    uint2 v[kHxsItems];
+};
+
+// Two half samples of one dword -> f32 (code: kSampF16 / kSampBF16, uniform).
+__device__ __forceinline__ f2v hxsHalf2(uint32_t u, int code) {
+    if (code == kSampBF16) return f2v{__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)};
+    typedef _Float16 h2v_ __attribute__((ext_vector_type(2)));
+    const h2v_ h = __builtin_bit_cast(h2v_, u);
+    return f2v{static_cast<float>(h.x), static_cast<float>(h.y)};
+}
 
 // Per-block load source: one resource from the block's first chunk row 0 (records end at the
 // caller's input end: zeros past it), the byte stride of a row and of a chunk.
@@ -388,13 +410,14 @@ __device__ __forceinline__ HxsRegSrc hxsRegSrc(XP x, int b, int lane) {
     const int col0 = b * (FMT == 5 ? 32 : 16), k = col0 / x->C, c0 = col0 - k * x->C;
     r.rowB = static_cast<int>(x->in_fs) * x->in_esz;
     r.chunkB = x->Np * x->Qc * r.rowB;
-    r.r = hxsRsrcT(x, hxsChunkRow(x, k, 0), (FMT == 2 || FMT == 5) ? c0 : 0,
-                   FMT == 5 ? 128 : FMT == 2 ? 64 : (FMT == 3 ? 4 : 8));
+    r.r = hxsRsrcT(x, hxsChunkRow(x, k, 0), (FMT == 2 || FMT == 5 || FMT == 7) ? c0 : 0,
+                   FMT == 5 ? 128 : FMT == 2 ? 64 : FMT == 7 ? 32 : ((FMT == 3 || FMT == 6) ? 4 : 8));
     // ROW16: lane = 16 q + r reads row r of a 16-row piece, channels 4q..4q+3 -- one instruction
     // covers 16 whole 64-B block rows (16 lines) instead of 16 B of 64 rows (64 lines); ROW32 (FMT 5,
     // hxt_kernel only): lane = 8 r + q, 8 whole 128-B rows per instruction
     r.lane0 = FMT == 5 ? (lane >> 3) * r.rowB + 16 * (lane & 7)
-            : FMT == 2 ? (lane & 15) * r.rowB + 16 * (lane >> 4) : lane * r.rowB;
+            : FMT == 2 ? (lane & 15) * r.rowB + 16 * (lane >> 4)
+            : FMT == 7 ? (lane & 15) * r.rowB + 8 * (lane >> 4) : lane * r.rowB;
     return r;
 }
 
@@ -421,12 +444,16 @@ __device__ __forceinline__ bool hxsRegIssue(const HxsStage& st, bool live, const
             const bool on16 = it < 4 * kHxsNP && 16 * it < (fast ? st.nrow : 0);
             const int o = on16 ? base + 16 * it * rq.rowB : static_cast<int>(0x80000000u);
             r.v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs.r, o, 0, 0));
+        } else if constexpr (FMT == 7) {  // item = 16-row piece of 32-B half rows
+            const bool on16 = it < 4 * kHxsNP && 16 * it < (fast ? st.nrow : 0);
+            const int o = on16 ? base + 16 * it * rq.rowB : static_cast<int>(0x80000000u);
+            r.v[k] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs.r, o, 0, 0));
         } else if constexpr (FMT == 1 || FMT == 4) {  // f32 / int32 stereo frames
             const int o = on ? base + 64 * i * rq.rowB + 2 * q * rq.chunkB : static_cast<int>(0x80000000u);
             const int o2 = on ? o + rq.chunkB : o;
             r.a[k] = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rs.r, o, 0, 0));
             r.b[k] = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rs.r, o2, 0, 0));
-        } else if constexpr (FMT == 3) {  // int16 stereo frames
+        } else if constexpr (FMT == 3 || FMT == 6) {  // int16 / half stereo frames
             const int o = on ? base + 64 * i * rq.rowB + 2 * q * rq.chunkB : static_cast<int>(0x80000000u);
             const int o2 = on ? o + rq.chunkB : o;
             r.a[k] = __builtin_amdgcn_raw_buffer_load_b32(rs.r, o, 0, 0);
@@ -500,11 +527,12 @@ __device__ __forceinline__ int32_t pcm16Of(float y) {
 // Interior store of a lane's four rows.  VST (the launch's output layout, a template parameter so
 // the epilogue carries no layout branches): 0 any f32 layout (4 stores), 1 channel-contiguous f32
 // (one 16-B store), 2 stereo-interleaved f32 (lane pairs swap halves by DPP: one 16-B store of two
-// frames each), 3 f64 (4 stores), 4 stereo-interleaved PCM16 (two int16 frames, 8 B).
+// frames each), 3 f64 (4 stores), 4 stereo-interleaved PCM16 (two int16 frames, 8 B), 5 stereo-
+// interleaved f16 / bf16 (two frames, 8 B: the same lane-pair swap, packed f32 -> half conversion).
 template <int VST>
 __device__ __forceinline__ void hxsStoreFast(const HxsArgs& x, char* p, f32x4 y, int lane) {
     const bool nt = kHxsDev && x.nt;
-    if (VST == 2 || VST == 4) {
+    if (VST == 2 || VST == 4 || VST == 5) {
         const bool even = (lane & 1) == 0;
         const float s0 = even ? y[2] : y[0], s1 = even ? y[3] : y[1];
         const float q0 = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s0), 0xB1, 0xf, 0xf, false));
@@ -517,6 +545,17 @@ __device__ __forceinline__ void hxsStoreFast(const HxsArgs& x, char* p, f32x4 y,
             uint2 v;
             v.x = (static_cast<uint32_t>(i0) & 0xffffu) | (static_cast<uint32_t>(i1) << 16);
             v.y = (static_cast<uint32_t>(i2) & 0xffffu) | (static_cast<uint32_t>(i3) << 16);
+            *reinterpret_cast<uint2*>(p) = v;
+        } else if constexpr (VST == 5) {  // two half stereo frames (8 B): one RNE each, no clamp
+            uint2 v;
+            if (x.out_pcm == kSampBF16) {
+                v.x = static_cast<uint32_t>(halfOfF32(w[0], kSampBF16)) | (static_cast<uint32_t>(halfOfF32(w[1], kSampBF16)) << 16);
+                v.y = static_cast<uint32_t>(halfOfF32(w[2], kSampBF16)) | (static_cast<uint32_t>(halfOfF32(w[3], kSampBF16)) << 16);
+            } else {
+                typedef _Float16 h2v_ __attribute__((ext_vector_type(2)));
+                v.x = __builtin_bit_cast(uint32_t, h2v_{static_cast<_Float16>(w[0]), static_cast<_Float16>(w[1])});
+                v.y = __builtin_bit_cast(uint32_t, h2v_{static_cast<_Float16>(w[2]), static_cast<_Float16>(w[3])});
+            }
             *reinterpret_cast<uint2*>(p) = v;
         } else if (nt) {
             __builtin_nontemporal_store(w, reinterpret_cast<f32x4*>(p));
@@ -574,6 +613,12 @@ __device__ __forceinline__ void hxsRegConvert(XP x, const HxsStage& st, bool fas
                 const int row = 16 * it + (lane & 15);
                 if (it < 4 * kHxsNP && 16 * it < st.nrow && row < st.nrow)
                     hxsPutItem(x, st, p0, lane >> 4, row, r.v[k], sh.ring, sh.QS, sh.loudLo, sh.loudHi, sh.flag);
+            } else if constexpr (FMT == 7) {
+                const int row = 16 * it + (lane & 15);
+                if (it < 4 * kHxsNP && 16 * it < st.nrow && row < st.nrow) {
+                    const f2v a = hxsHalf2(r.v[k].x, x->in_pcm), c = hxsHalf2(r.v[k].y, x->in_pcm);
+                    hxsPutItem(x, st, p0, lane >> 4, row, f32x4{a.x, a.y, c.x, c.y}, sh.ring, sh.QS, sh.loudLo, sh.loudHi, sh.flag);
+                }
             } else if (it < 4 * kHxsNP && 64 * i < st.nrow) {  // uniform
                 f32x4 e;
                 if constexpr (FMT == 1) {
@@ -584,6 +629,9 @@ __device__ __forceinline__ void hxsRegConvert(XP x, const HxsStage& st, bool fas
                               static_cast<float>(pcmToF64(static_cast<int16_t>(ua >> 16), 16)),
                               static_cast<float>(pcmToF64(static_cast<int16_t>(ub & 0xffffu), 16)),
                               static_cast<float>(pcmToF64(static_cast<int16_t>(ub >> 16), 16))};
+                } else if constexpr (FMT == 6) {  // f16 / bf16 pairs: exact widening
+                    const f2v a = hxsHalf2(r.a[k], x->in_pcm), c = hxsHalf2(r.b[k], x->in_pcm);
+                    e = f32x4{a.x, a.y, c.x, c.y};
                 } else {  // FMT 4: int32 pairs (PCM24 / PCM32)
                     const int bits = x->in_pcm;
                     e = f32x4{static_cast<float>(pcmToF64(__builtin_bit_cast(int32_t, r.a[k].x), bits)),
@@ -642,8 +690,8 @@ __device__ __forceinline__ void hxsGroups(const HxsArgs& x, const HxsShared& sh_
             const int64_t a = aCol + p;
             const int64_t o0 = a * x.Pc + oRow0;
             const bool live = colOk && p < x.Np && a < x.a_hi;
-            if (fullRb && live && (!x.out_pcm || VST == 4) && a * x.Pc >= x.o_lo && (a + 1) * x.Pc <= x.o_hi) {
-                char* pp = x.out + (o0 + (((VST == 2 || VST == 4) && (lane & 1)) ? 2 : 0)) * x.out_fs + ((VST == 2 || VST == 4) ? 0 : ccol * x.out_cs);
+            if (fullRb && live && (!x.out_pcm || VST == 4 || VST == 5) && a * x.Pc >= x.o_lo && (a + 1) * x.Pc <= x.o_hi) {
+                char* pp = x.out + (o0 + (((VST == 2 || VST == 4 || VST == 5) && (lane & 1)) ? 2 : 0)) * x.out_fs + ((VST == 2 || VST == 4 || VST == 5) ? 0 : ccol * x.out_cs);
                 hxsStoreFast<VST>(x, pp, y, lane);
             } else if (live) {
 #pragma unroll
@@ -777,10 +825,10 @@ __device__ __forceinline__ void hxsCompute(const HxsArgs& x, const HxsShared& sh
         const int kcol = col / x.C, ccol = col - kcol * x.C;
         const int64_t aCol = x.a_lo + static_cast<int64_t>(kcol) * x.Np;
         const int64_t oRow0 = static_cast<int64_t>(rbw) * 16 + 4 * grp;  // first row of this lane's accumulator
-        const bool laneFast = fullRb && colOk && (!x.out_pcm || VST == 4) && aCol + x.Np <= x.a_hi &&
+        const bool laneFast = fullRb && colOk && (!x.out_pcm || VST == 4 || VST == 5) && aCol + x.Np <= x.a_hi &&
                               aCol * x.Pc >= x.o_lo && (aCol + x.Np) * x.Pc <= x.o_hi;
-        char* obase = x.out + (aCol * x.Pc + oRow0 + (((VST == 2 || VST == 4) && (lane & 1)) ? 2 : 0)) * x.out_fs +
-                      ((VST == 2 || VST == 4) ? 0 : ccol * x.out_cs);
+        char* obase = x.out + (aCol * x.Pc + oRow0 + (((VST == 2 || VST == 4 || VST == 5) && (lane & 1)) ? 2 : 0)) * x.out_fs +
+                      ((VST == 2 || VST == 4 || VST == 5) ? 0 : ccol * x.out_cs);
         if (__builtin_amdgcn_ballot_w64(!laneFast) == 0)
             hxsGroups<NS, VST, true>(x, sh_, lane, Ah, Al, laneOff, u0, P, nslot, obase, pstride, aCol, oRow0, colOk,
                                      ccol, fullRb, tm, tw);
@@ -869,7 +917,8 @@ __device__ __forceinline__ void hxsRegLoadersT(const HxsArgs& x, const HxsShared
                     for (int k = 0; k < kHxsItems; ++k) {
                         if constexpr (FMT == 2) s += buf[d].v[k][0] + buf[d].v[k][3];
                         else if constexpr (FMT == 1 || FMT == 4) s += buf[d].a[k].x + buf[d].b[k].y;
-                        else if constexpr (FMT == 3) s += static_cast<float>(buf[d].a[k] ^ buf[d].b[k]);
+                        else if constexpr (FMT == 3 || FMT == 6) s += static_cast<float>(buf[d].a[k] ^ buf[d].b[k]);
+                        else if constexpr (FMT == 7) s += static_cast<float>(buf[d].v[k].x ^ buf[d].v[k].y);
                     }
                     if (s == 1234.5f) sh_.loudLo[0] = 0;
                 } else if (j < nL && !((dbg & 16) && j >= P)) {
@@ -899,6 +948,8 @@ __device__ __forceinline__ void hxsRegLoaders(const HxsArgs& x, const HxsShared&
     else if (x.fmt == 2) hxsRegLoadersT<2>(x, sh_, l, lane);
     else if (x.fmt == 3) hxsRegLoadersT<3>(x, sh_, l, lane);
     else if (x.fmt == 4) hxsRegLoadersT<4>(x, sh_, l, lane);
+    else if (x.fmt == 6) hxsRegLoadersT<6>(x, sh_, l, lane);
+    else if (x.fmt == 7) hxsRegLoadersT<7>(x, sh_, l, lane);
     else hxsRegLoadersT<0>(x, sh_, l, lane);
 }
 
@@ -957,9 +1008,9 @@ __device__ __forceinline__ void hxsSmallOut(const HxsArgs& x, uint32_t aH, uint3
     const bool fullRb = (rbw + 1) * 16 <= x.Pc;
     const bool live = colOk && a < x.a_hi;
     // whole-period stores need both lanes of a stereo pair (same chunk: same condition)
-    if (fullRb && live && (!x.out_pcm || VST == 4) && a * x.Pc >= x.o_lo && (a + 1) * x.Pc <= x.o_hi) {
-        char* pp = x.out + (o0 + (((VST == 2 || VST == 4) && (lane & 1)) ? 2 : 0)) * x.out_fs +
-                   ((VST == 2 || VST == 4) ? 0 : ccol * x.out_cs);
+    if (fullRb && live && (!x.out_pcm || VST == 4 || VST == 5) && a * x.Pc >= x.o_lo && (a + 1) * x.Pc <= x.o_hi) {
+        char* pp = x.out + (o0 + (((VST == 2 || VST == 4 || VST == 5) && (lane & 1)) ? 2 : 0)) * x.out_fs +
+                   ((VST == 2 || VST == 4 || VST == 5) ? 0 : ccol * x.out_cs);
         hxsStoreFast<VST>(x, pp, y, lane);
     } else if (live) {
 #pragma unroll
@@ -1401,7 +1452,13 @@ hipError_t hxsLaunch(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t s
 #define GAR_HXS_FOR_LO(M) GAR_HXS_FOR4(M, 1) GAR_HXS_FOR4(M, 2) GAR_HXS_FOR4(M, 3) GAR_HXS_FOR4(M, 4) GAR_HXS_FOR4(M, 5)
 #define GAR_HXS_FOR_HI(M) GAR_HXS_FOR4(M, 6) GAR_HXS_FOR4(M, 7) GAR_HXS_FOR4(M, 8) GAR_HXS_FOR4(M, 9) GAR_HXS_FOR4(M, 10)
 #endif
-#define GAR_HXS_FOR_ALL(M) GAR_HXS_FOR_LO(M) GAR_HXS_FOR_HI(M)
+// VST 5 (half frame pairs): a build unit of its own (gar_hxs_i3.hip)
+#if GAR_HXS_QUICK
+#define GAR_HXS_FOR_HALF(M) M(9, 5) M(10, 5)
+#else
+#define GAR_HXS_FOR_HALF(M) M(1, 5) M(2, 5) M(3, 5) M(4, 5) M(5, 5) M(6, 5) M(7, 5) M(8, 5) M(9, 5) M(10, 5)
+#endif
+#define GAR_HXS_FOR_ALL(M) GAR_HXS_FOR_LO(M) GAR_HXS_FOR_HI(M) GAR_HXS_FOR_HALF(M)
 #define GAR_HXS_INST(NS, V) template hipError_t hxsLaunch<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t);
 
 }  // namespace gar

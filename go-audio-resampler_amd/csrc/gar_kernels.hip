@@ -640,9 +640,9 @@ __global__ __launch_bounds__(256) void convert_kernel(const void* s, int st, int
         const int64_t t = idx / C;
         const int c = static_cast<int>(idx - t * C);
         const int64_t se = t * sfs + c * scs, de = t * dfs + c * dcs;
-        const double v = st >= 16 ? pcmRead(s, se, st)
+        const double v = st >= kSampF16 ? pcmRead(s, se, st)
                                   : (st == 1 ? static_cast<const double*>(s)[se] : static_cast<double>(static_cast<const float*>(s)[se]));
-        if (dt >= 16) pcmWrite(d, de, dt, v);
+        if (dt >= kSampF16) pcmWrite(d, de, dt, v);  // half: one rounding from f64
         else if (dt == 1) static_cast<double*>(d)[de] = v;
         else static_cast<float*>(d)[de] = static_cast<float>(v);
     }

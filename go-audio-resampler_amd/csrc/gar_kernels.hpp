@@ -20,7 +20,7 @@ struct SrcDesc {
     const void* in;
     int64_t in_base, in_len, in_fs, in_cs;
     int in_f64;
-    int in_pcm;            // 0 float input, else PCM bits (16: int16, 24/32: int32 storage)
+    int in_pcm;            // 0 float input, else PCM bits (16: int16, 24/32: int32 storage) or 4 / 5: f16 / bf16
     int64_t valid_end;
 };
 
@@ -29,7 +29,7 @@ struct OutDesc {
     void* out;
     int64_t o0, fs, cs;
     int f64;
-    int pcm;               // 0 float output, else PCM bits (int(clamp(y, -1, 1) * maxVal))
+    int pcm;               // 0 float output, else PCM bits (int(clamp(y, -1, 1) * maxVal)) or 4 / 5: f16 / bf16 (RNE)
     int64_t o_lo, o_hi;
     int* err;              // the calling handle's device status word (host-mapped), null if none
 };
@@ -39,12 +39,49 @@ struct OutDesc {
 __host__ __device__ inline double pcmMax(int bits) {
     return bits == 16 ? 32767.0 : (bits == 24 ? 8388607.0 : 2147483647.0);
 }
-__host__ __device__ inline int pcmBytes(int bits) { return bits == 16 ? 2 : 4; }
+// Half-precision samples (gar.h GAR_F16 / GAR_BF16) travel in the same fields as the PCM bits
+// (SrcDesc::in_pcm, OutDesc::pcm, launchConvert's type codes) under their ABI codes 4 and 5, below
+// every PCM width.  In: exact widening (f16 subnormals are values).  Out: ONE round-to-nearest-even
+// from the compute type -- overflow gives +-Inf (no clamp), NaN stays NaN, subnormals are produced.
+// From f64 that is f64 -> f32 rounded to odd, then f32 -> half to nearest-even: the odd last bit
+// keeps the inexactness the second rounding must see, so the pair equals a single f64 -> half RNE.
+constexpr int kSampF16 = 4, kSampBF16 = 5;
+__host__ __device__ inline bool sampIsHalf(int t) { return t == kSampF16 || t == kSampBF16; }
+__host__ __device__ inline float halfToF32(uint16_t b, int code) {
+    if (code == kSampBF16) return __builtin_bit_cast(float, static_cast<uint32_t>(b) << 16);
+    return static_cast<float>(__builtin_bit_cast(_Float16, b));
+}
+__host__ __device__ inline uint16_t halfOfF32(float v, int code) {
+    if (code == kSampBF16) {
+        uint32_t u = __builtin_bit_cast(uint32_t, v);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40u);  // NaN stays NaN
+        u += 0x7fffu + ((u >> 16) & 1u);  // nearest even; a carry out of the mantissa reaches Inf
+        return static_cast<uint16_t>(u >> 16);
+    }
+    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v));
+}
+__host__ __device__ inline float f32OddOfF64(double d) {
+    const float f = static_cast<float>(d);
+    if (d != d || static_cast<double>(f) == d) return f;
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if (u & 1u) return f;  // the nearest float is the odd neighbour already
+    const double af = f < 0 ? -static_cast<double>(f) : static_cast<double>(f), ad = d < 0 ? -d : d;
+    u += af > ad ? ~0u : 1u;  // the other neighbour (sign-magnitude: +-1 on the bits); Inf -> largest finite
+    return __builtin_bit_cast(float, u);
+}
+__host__ __device__ inline uint16_t halfOfF64(double d, int code) { return halfOfF32(f32OddOfF64(d), code); }
+
+__host__ __device__ inline int pcmBytes(int bits) { return bits <= 16 ? 2 : 4; }
 __host__ __device__ inline double pcmToF64(int32_t i, int bits) { return static_cast<double>(i) * (1.0 / pcmMax(bits)); }
 __host__ __device__ inline double pcmRead(const void* p, int64_t e, int bits) {
+    if (sampIsHalf(bits)) return static_cast<double>(halfToF32(static_cast<const uint16_t*>(p)[e], bits));
     return bits == 16 ? pcmToF64(static_cast<const int16_t*>(p)[e], 16) : pcmToF64(static_cast<const int32_t*>(p)[e], bits);
 }
 __host__ __device__ inline void pcmWrite(void* p, int64_t e, int bits, double y) {
+    if (sampIsHalf(bits)) {
+        static_cast<uint16_t*>(p)[e] = halfOfF64(y, bits);
+        return;
+    }
     const double v = y > 1.0 ? 1.0 : (y < -1.0 ? -1.0 : y);  // NaN passes through as in Go, then converts
     const double s = v * pcmMax(bits);
     if (bits == 16) static_cast<int16_t*>(p)[e] = static_cast<int16_t>(s == s ? static_cast<int32_t>(s) : 0);
@@ -166,7 +203,8 @@ hipError_t launchGather(int f64, const SrcDesc& src, void* dst, int64_t t0, int6
 // Strided copy with dtype conversion (pass-through stages, group split).
 hipError_t launchCopy(const void* src, int src_f64, int64_t s_fs, int64_t s_cs, void* dst, int dst_f64,
                       int64_t d_fs, int64_t d_cs, int64_t n, int C, hipStream_t stream);
-// PCM staging of the non-fused paths: type codes 0 f32, 1 f64, 16/24/32 PCM (pcmRead / pcmWrite).
+// PCM / half staging of the non-fused paths: type codes 0 f32, 1 f64, 4 f16, 5 bf16, 16/24/32 PCM
+// (pcmRead / pcmWrite); not the ABI's codes for f32 / f64.
 hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs, void* dst, int d_type, int64_t d_fs,
                          int64_t d_cs, int64_t n, int C, hipStream_t stream);
 

@@ -90,7 +90,7 @@ EXPORTED = [
     "gar_device_flush_size", "gar_reset", "gar_get_ratio", "gar_get_latency", "gar_get_info", "gar_channels",
     "gar_status_string", "gar_last_error", "gar_design_engine", "gar_design_composite", "gar_profile_enable",
     "gar_profile_read", "gar_stage_state", "gar_num_stages", "gar_stage_geometry", "gar_get_statistics",
-    "gar_synchronize", "gar_profile_launch_stats", "gar_profile_kinds",
+    "gar_synchronize", "gar_profile_launch_stats", "gar_profile_kinds", "gar_dev_half_convert",
 ]
 
 _lib = None
@@ -155,6 +155,7 @@ def lib():
         "gar_synchronize": (i32, [vp]),
         "gar_profile_kinds": (None, [vp, C.c_uint32]),
         "gar_profile_launch_stats": (i32, [vp, i32, C.POINTER(d), C.POINTER(d), C.POINTER(d)]),
+        "gar_dev_half_convert": (i32, [i32, vp, i64, vp, vp, vp]),
     }
     ab = os.environ.get("GAR_LIB_PATH") is not None
     for name, (res, args) in sig.items():
@@ -348,10 +349,12 @@ class Resampler:
 
     # -- device-resident (torch tensors on cuda) --
     def process_device(self, x, out=None, stream=None, pcm_bits=None):
-        """x: [frames, channels] device tensor (float32/float64, or integer PCM: int16 = PCM16,
-        int32 = PCM24/PCM32 per pcm_bits, default 32), any strides.  Returns out[:n] (out
-        allocated with x's dtype if None).  Integer PCM follows cmd/resample-wav/main.go:444-543
-        (input i * (1/maxVal), output int(clamp(y, -1, 1) * maxVal)).
+        """x: [frames, channels] device tensor (float32/float64, float16/bfloat16, or integer PCM:
+        int16 = PCM16, int32 = PCM24/PCM32 per pcm_bits, default 32), any strides.  Returns out[:n]
+        (out allocated with x's dtype if None; x and out may differ in dtype).  Integer PCM follows
+        cmd/resample-wav/main.go:444-543 (input i * (1/maxVal), output int(clamp(y, -1, 1) * maxVal)).
+        float16 / bfloat16 samples are widened exactly on input and rounded once, to nearest even, on
+        output (overflow gives +-Inf, no clamp; gar.h GAR_F16 / GAR_BF16).
         x.shape[1] (and out.shape[1]) must equal Channels (ErrChannelMismatch)."""
         import torch
         assert x.is_cuda and x.dim() == 2
@@ -374,6 +377,8 @@ class Resampler:
         return out[: got.value]
 
     def flush_device(self, out=None, dtype=None, stream=None, pcm_bits=None):
+        """Flush all channels into a device tensor (FlushMulti semantics): `out`, or a new tensor of
+        `dtype` (default float32; any sample type process_device takes, float16 / bfloat16 included)."""
         import torch
         if out is not None and out.shape[1] != self.Channels:
             raise ErrChannelMismatch(f"expected {self.Channels} channels, got {out.shape[1]}")
@@ -391,15 +396,20 @@ class Resampler:
 
 
 PCM16, PCM24, PCM32 = 16, 24, 32
+F16, BF16 = 4, 5  # device sample types only (gar.h GAR_F16 / GAR_BF16), not compute types
 
 
 def _io_type(dtype, pcm_bits=None):
-    """Device sample type code of a torch dtype (gar.h GAR_F32/GAR_F64/GAR_PCM*)."""
+    """Device sample type code of a torch dtype (gar.h GAR_F32/GAR_F64/GAR_F16/GAR_BF16/GAR_PCM*)."""
     import torch
     if dtype == torch.float64:
         return F64
     if dtype == torch.float32:
         return F32
+    if dtype == torch.float16:
+        return F16
+    if dtype == torch.bfloat16:
+        return BF16
     if dtype == torch.int16:
         return PCM16
     if dtype == torch.int32:
@@ -408,6 +418,16 @@ def _io_type(dtype, pcm_bits=None):
             raise ValueError("int32 PCM holds 24- or 32-bit samples")
         return bits
     raise TypeError(f"unsupported sample dtype {dtype}")
+
+
+def half_convert(x, half_type):
+    """Host run of the kernels' half conversions (gar.h gar_dev_half_convert) on the float64 array x:
+    (bits of one f64 -> half rounding, bits of float32(x) -> half, those first bits widened to f32)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    a, b = np.zeros(x.size, dtype=np.uint16), np.zeros(x.size, dtype=np.uint16)
+    w = np.zeros(x.size, dtype=np.float32)
+    _check(lib().gar_dev_half_convert(int(half_type), _p(x), x.size, _p(a), _p(b), _p(w)))
+    return a, b, w
 
 
 def New(config):

@@ -59,6 +59,22 @@ enum { GAR_F64 = 0, GAR_F32 = 1, GAR_F32_EXACT = 2 };
  * Fused into the split-f16 kernel's loads and stores for single-stage float32 plans; staged
  * through a conversion kernel otherwise. */
 enum { GAR_PCM16 = 16, GAR_PCM24 = 24, GAR_PCM32 = 32 };
+/* half-precision sample types of the device entry points (in_dtype / out_dtype of gar_process_device
+ * and gar_flush_device only; independent of each other and of the compute type: f16 in / f32 out,
+ * PCM16 in / bf16 out, ... are all legal).  IEEE binary16 and bfloat16, 2 bytes per sample; the value
+ * 3 stays unassigned.  They are not compute types: gar_config_validate, gar_new and gar_new_batch
+ * answer GAR_ERR_INVALID_CONFIG for them as compute_dtype.  The host-memory entry points have no
+ * half form (Go has no half type).
+ *   input:  exact widening to the compute type.  f16 subnormals are values (not flushed); Inf and
+ *           NaN enter the non-finite handling and |x| >= 16 the loud handling described for GAR_F32.
+ *   output: ONE round-to-nearest-even from the compute type to the half type.  Values past the
+ *           largest finite half become +-Inf (no clamp, unlike PCM); NaN stays NaN (payload
+ *           unspecified); subnormal results are produced, not flushed.  With float64 compute the
+ *           rounding is f64 -> half directly (f64 -> f32 to odd, then f32 -> half to nearest-even),
+ *           never f64 -> f32 -> half with two nearest roundings.
+ * Fused into the split-f16 kernel's loads and stores wherever PCM is (a stereo frame is one dword,
+ * like a PCM16 frame); staged through the conversion kernel otherwise. */
+enum { GAR_F16 = 4, GAR_BF16 = 5 };
 /* engine.Quality (internal/engine/filter_params.go:16-41), for gar_design_engine */
 enum { GAR_ENGINE_QUICK = 0, GAR_ENGINE_LOW, GAR_ENGINE_MEDIUM, GAR_ENGINE_HIGH, GAR_ENGINE_VERYHIGH,
        GAR_ENGINE_16BIT, GAR_ENGINE_20BIT, GAR_ENGINE_24BIT, GAR_ENGINE_28BIT, GAR_ENGINE_32BIT };
@@ -237,6 +253,14 @@ gar_status gar_stage_state(const gar_resampler *r, int32_t stage, int32_t *fused
  * at a time uses the workers, the others run inline) and check every element.  0 = every element
  * right; else the number of wrong elements.  For tests (CPU suite; tools/asan_tests.sh with TSan). */
 int64_t gar_dev_pool_selftest(int32_t threads, int32_t iters, int32_t channels, int64_t frames);
+
+/* The sample conversions of GAR_F16 / GAR_BF16 run on the host (no GPU; the kernels use the same
+ * functions): for each in[i], from_f64[i] = the half bit pattern of ONE rounding f64 -> half (what a
+ * float64-compute handle stores), from_f32[i] = the pattern of float32(in[i]) rounded to half (what a
+ * float32-compute handle stores), widened[i] = from_f64[i] widened back to float32 (the input
+ * conversion).  Any output may be NULL.  For tests (CPU suite). */
+gar_status gar_dev_half_convert(int32_t half_type, const double *in, int64_t n, uint16_t *from_f64,
+                                uint16_t *from_f32, float *widened);
 
 /* ---- host-only design introspection (no GPU needed) ----------------------- */
 typedef struct gar_engine_geometry {

@@ -1275,6 +1275,8 @@ gar_status validate(const gar_config* c) {
     if (c->channels > 256) return guard(GAR_ERR_INVALID_CONFIG, "invalid resampler configuration: too many channels (max 256)");
     if (c->compute_dtype == GAR_F16 || c->compute_dtype == GAR_BF16)
         return guard(GAR_ERR_INVALID_CONFIG, "invalid resampler configuration: f16 / bf16 are sample types of the device entry points, not compute types");
+    if (c->compute_dtype == GAR_PCM24_PACKED)
+        return guard(GAR_ERR_INVALID_CONFIG, "invalid resampler configuration: packed 24-bit PCM is a sample type of the device entry points, not a compute type");
     const double r = c->output_rate / c->input_rate;
     if (r < 1.0 / 256.0 || r > 256.0)
         return guard(GAR_ERR_INVALID_CONFIG, "invalid resampler configuration: resampling ratio out of range");
@@ -1532,7 +1534,7 @@ gar_status monoCall(Handle* h, int ch, const T* in, int64_t n, T* out, int64_t c
 
 namespace gar {
 namespace {
-bool isPcm(int32_t t) { return t == GAR_PCM16 || t == GAR_PCM24 || t == GAR_PCM32; }
+bool isPcm(int32_t t) { return t == GAR_PCM16 || t == GAR_PCM24 || t == GAR_PCM32 || t == GAR_PCM24_PACKED; }
 bool isHalf(int32_t t) { return t == GAR_F16 || t == GAR_BF16; }
 // sample types converted at the device entry points: integer PCM and f16 / bf16 (InView::pcm / OutView::pcm
 // carry the ABI code, which is also launchConvert's code for them)
@@ -1866,7 +1868,10 @@ gar_status gar_process_device(gar_resampler* r, const void* in, int32_t in_dtype
     if (r->groups.size() != 1) return guard(GAR_ERR_NOT_SUPPORTED, "channels are not in lockstep (per-channel calls were made)");
     return callOn(r, static_cast<hipStream_t>(stream), [&]() -> gar_status {
         hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = legacy default stream
-        const bool fuse = pcmFusable(r);
+        // packed 24-bit PCM is always staged (pack24_kernel / unpack24_kernel / convert_kernel): hxs_kernel has no
+        // 3-byte load or store layout
+        const bool fuseAny = pcmFusable(r);
+        bool fuse = fuseAny && in_dtype != GAR_PCM24_PACKED;
         InView iv;
         iv.p = in;
         iv.f64 = in_dtype == GAR_F64 ? 1 : 0;
@@ -1887,6 +1892,7 @@ gar_status gar_process_device(gar_resampler* r, const void* in, int32_t in_dtype
                 iv.cs = 1;
             }
         }
+        fuse = fuseAny && out_dtype != GAR_PCM24_PACKED;
         OutView ov;
         ov.p = out;
         ov.f64 = out_dtype == GAR_F64 ? 1 : 0;
@@ -1929,7 +1935,7 @@ gar_status gar_flush_device(gar_resampler* r, int32_t channels, void* out, int32
     if (r->groups.size() != 1) return guard(GAR_ERR_NOT_SUPPORTED, "channels are not in lockstep");
     return callOn(r, static_cast<hipStream_t>(stream), [&]() -> gar_status {
         hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = legacy default stream
-        const bool fuse = pcmFusable(r);
+        const bool fuse = pcmFusable(r) && out_dtype != GAR_PCM24_PACKED;  // packed 24-bit PCM is always staged
         OutView ov;
         ov.p = out;
         ov.f64 = out_dtype == GAR_F64 ? 1 : 0;
@@ -2104,6 +2110,18 @@ gar_status gar_dev_half_convert(int32_t half_type, const double* in, int64_t n, 
         if (from_f64) from_f64[i] = b;
         if (from_f32) from_f32[i] = halfOfF32(static_cast<float>(in[i]), half_type);
         if (widened) widened[i] = halfToF32(b, half_type);
+    }
+    return GAR_OK;
+}
+
+gar_status gar_dev_pcm24_convert(const double* in, int64_t n, uint8_t* packed, int32_t* unpacked) {
+    if (n < 0 || (n > 0 && !in)) return guard(GAR_ERR_INVALID_ARGUMENT, "bad packed 24-bit conversion arguments");
+    static_assert(kSampPcm24P == GAR_PCM24_PACKED, "the kernels' packed 24-bit code is the ABI's");
+    for (int64_t i = 0; i < n; ++i) {
+        uint8_t b[3];
+        pcmWrite(b, 0, kSampPcm24P, in[i]);  // what convert_kernel / pack24_kernel store from f64
+        if (packed) std::memcpy(packed + 3 * i, b, 3);
+        if (unpacked) unpacked[i] = pcm24Load(b);
     }
     return GAR_OK;
 }

@@ -381,6 +381,10 @@ struct HxsRegBuf<3> {  // STEREO PCM16: one dword (both channels) per chunk row
     uint32_t a[kHxsItems], b[kHxsItems];
 };
 template <>
+struct HxsRegBuf<4> {  // STEREO int32 PCM24 / PCM32: both channels of a chunk row, kept as integers
+    uint2 a[kHxsItems], b[kHxsItems];
+};
+template <>
 struct HxsRegBuf<6> {  // STEREO f16 / bf16: one dword (both channels) per chunk row
     uint32_t a[kHxsItems], b[kHxsItems];
 };
@@ -448,11 +452,17 @@ __device__ __forceinline__ bool hxsRegIssue(const HxsStage& st, bool live, const
             const bool on16 = it < 4 * kHxsNP && 16 * it < (fast ? st.nrow : 0);
             const int o = on16 ? base + 16 * it * rq.rowB : static_cast<int>(0x80000000u);
             r.v[k] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs.r, o, 0, 0));
-        } else if constexpr (FMT == 1 || FMT == 4) {  // f32 / int32 stereo frames
+        } else if constexpr (FMT == 1) {  // f32 stereo frames
             const int o = on ? base + 64 * i * rq.rowB + 2 * q * rq.chunkB : static_cast<int>(0x80000000u);
             const int o2 = on ? o + rq.chunkB : o;
             r.a[k] = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rs.r, o, 0, 0));
             r.b[k] = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rs.r, o2, 0, 0));
+        } else if constexpr (FMT == 4) {  // int32 stereo frames, in integer registers: carried through a float vector
+            // the second channel's conversion was dropped (both channels came out as channel 0)
+            const int o = on ? base + 64 * i * rq.rowB + 2 * q * rq.chunkB : static_cast<int>(0x80000000u);
+            const int o2 = on ? o + rq.chunkB : o;
+            r.a[k] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs.r, o, 0, 0));
+            r.b[k] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs.r, o2, 0, 0));
         } else if constexpr (FMT == 3 || FMT == 6) {  // int16 / half stereo frames
             const int o = on ? base + 64 * i * rq.rowB + 2 * q * rq.chunkB : static_cast<int>(0x80000000u);
             const int o2 = on ? o + rq.chunkB : o;
@@ -634,10 +644,10 @@ __device__ __forceinline__ void hxsRegConvert(XP x, const HxsStage& st, bool fas
                     e = f32x4{a.x, a.y, c.x, c.y};
                 } else {  // FMT 4: int32 pairs (PCM24 / PCM32)
                     const int bits = x->in_pcm;
-                    e = f32x4{static_cast<float>(pcmToF64(__builtin_bit_cast(int32_t, r.a[k].x), bits)),
-                              static_cast<float>(pcmToF64(__builtin_bit_cast(int32_t, r.a[k].y), bits)),
-                              static_cast<float>(pcmToF64(__builtin_bit_cast(int32_t, r.b[k].x), bits)),
-                              static_cast<float>(pcmToF64(__builtin_bit_cast(int32_t, r.b[k].y), bits))};
+                    e = f32x4{static_cast<float>(pcmToF64(static_cast<int32_t>(r.a[k].x), bits)),
+                              static_cast<float>(pcmToF64(static_cast<int32_t>(r.a[k].y), bits)),
+                              static_cast<float>(pcmToF64(static_cast<int32_t>(r.b[k].x), bits)),
+                              static_cast<float>(pcmToF64(static_cast<int32_t>(r.b[k].y), bits))};
                 }
                 const int row = 64 * i + lane;
                 if (row < st.nrow) hxsPutItem(x, st, p0, q, row, e, sh.ring, sh.QS, sh.loudLo, sh.loudHi, sh.flag);
@@ -916,7 +926,8 @@ __device__ __forceinline__ void hxsRegLoadersT(const HxsArgs& x, const HxsShared
 #pragma unroll
                     for (int k = 0; k < kHxsItems; ++k) {
                         if constexpr (FMT == 2) s += buf[d].v[k][0] + buf[d].v[k][3];
-                        else if constexpr (FMT == 1 || FMT == 4) s += buf[d].a[k].x + buf[d].b[k].y;
+                        else if constexpr (FMT == 1) s += buf[d].a[k].x + buf[d].b[k].y;
+                        else if constexpr (FMT == 4) s += static_cast<float>(buf[d].a[k].x ^ buf[d].b[k].y);
                         else if constexpr (FMT == 3 || FMT == 6) s += static_cast<float>(buf[d].a[k] ^ buf[d].b[k]);
                         else if constexpr (FMT == 7) s += static_cast<float>(buf[d].v[k].x ^ buf[d].v[k].y);
                     }

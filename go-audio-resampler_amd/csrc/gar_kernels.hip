@@ -648,9 +648,90 @@ __global__ __launch_bounds__(256) void convert_kernel(const void* s, int st, int
     }
 }
 
+// Packed 24-bit PCM <-> a contiguous buffer of T (float / double): thread q converts samples 4q .. 4q+3,
+// i.e. the three whole dwords 3q .. 3q+2 of the packed side (12 B: one dwordx3 access from a 4-byte aligned
+// base) and one 16-B (float) or two 16-B (double) accesses of the other side.  The total % 4 samples after
+// the last whole quad go through pcmRead / pcmWrite, byte by byte, so no access reaches past the last sample.
+template <class T>
+__global__ __launch_bounds__(256) void unpack24_kernel(const uint8_t* s, T* d, int64_t total) {
+    typedef T tx2 __attribute__((ext_vector_type(2)));
+    typedef T tx4 __attribute__((ext_vector_type(4)));
+    const int64_t nq = total >> 2;
+    for (int64_t q = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; q <= nq;
+         q += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        if (q == nq) {  // checked tail
+            for (int64_t e = 4 * nq; e < total; ++e) d[e] = static_cast<T>(pcmRead(s, e, kSampPcm24P));
+            break;
+        }
+        const u32x3a v = *reinterpret_cast<const u32x3a*>(s + 12 * q);
+        const uint32_t w[3] = {v.x, v.y, v.z};
+        int32_t i[4];
+        pcm24Unpack4(w, i);
+        T y[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = static_cast<T>(pcmToF64(i[k], 24));
+        if constexpr (sizeof(T) == 4) {
+            *reinterpret_cast<tx4*>(d + 4 * q) = tx4{y[0], y[1], y[2], y[3]};
+        } else {
+            *reinterpret_cast<tx2*>(d + 4 * q) = tx2{y[0], y[1]};
+            *reinterpret_cast<tx2*>(d + 4 * q + 2) = tx2{y[2], y[3]};
+        }
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void pack24_kernel(const T* s, uint8_t* d, int64_t total) {
+    typedef T tx2 __attribute__((ext_vector_type(2)));
+    typedef T tx4 __attribute__((ext_vector_type(4)));
+    const int64_t nq = total >> 2;
+    for (int64_t q = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; q <= nq;
+         q += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        if (q == nq) {  // checked tail
+            for (int64_t e = 4 * nq; e < total; ++e) pcmWrite(d, e, kSampPcm24P, static_cast<double>(s[e]));
+            break;
+        }
+        T y[4];
+        if constexpr (sizeof(T) == 4) {
+            const tx4 v = *reinterpret_cast<const tx4*>(s + 4 * q);
+            y[0] = v.x; y[1] = v.y; y[2] = v.z; y[3] = v.w;
+        } else {
+            const tx2 a = *reinterpret_cast<const tx2*>(s + 4 * q), b = *reinterpret_cast<const tx2*>(s + 4 * q + 2);
+            y[0] = a.x; y[1] = a.y; y[2] = b.x; y[3] = b.y;
+        }
+        int32_t i[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) i[k] = pcmOfF64(static_cast<double>(y[k]), 24);
+        uint32_t w[3];
+        pcm24Pack4(i, w);
+        *reinterpret_cast<u32x3a*>(d + 12 * q) = u32x3a{w[0], w[1], w[2]};
+    }
+}
+
 hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs, void* dst, int d_type, int64_t d_fs,
                          int64_t d_cs, int64_t n, int C, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
+    // packed 24-bit, interleaved contiguous from a 4-byte aligned base, against contiguous f32 / f64 (16-B aligned):
+    // the vector kernels (knob GAR_PACK24_VEC=0, read per launch for A/B timing: the per-element kernel)
+    const bool contig = s_cs == 1 && s_fs == C && d_cs == 1 && d_fs == C;
+    const uintptr_t sA = reinterpret_cast<uintptr_t>(src), dA = reinterpret_cast<uintptr_t>(dst);
+    const bool unpackV = s_type == kSampPcm24P && d_type <= 1 && contig && (sA & 3) == 0 && (dA & 15) == 0;
+    const bool packV = d_type == kSampPcm24P && s_type <= 1 && contig && (dA & 3) == 0 && (sA & 15) == 0;
+    if (unpackV || packV) {
+        const char* e = std::getenv("GAR_PACK24_VEC");
+        if (!e || std::atoi(e) != 0) {
+            const int64_t total = n * C;
+            int64_t vb = ((total >> 2) + 1 + 255) / 256;
+            if (vb > 65536) vb = 65536;
+            const dim3 g(static_cast<unsigned>(vb)), b(256);
+            const uint8_t* sp = static_cast<const uint8_t*>(src);
+            uint8_t* dp = static_cast<uint8_t*>(dst);
+            if (unpackV && d_type == 1) hipLaunchKernelGGL(unpack24_kernel<double>, g, b, 0, stream, sp, static_cast<double*>(dst), total);
+            else if (unpackV) hipLaunchKernelGGL(unpack24_kernel<float>, g, b, 0, stream, sp, static_cast<float*>(dst), total);
+            else if (s_type == 1) hipLaunchKernelGGL(pack24_kernel<double>, g, b, 0, stream, static_cast<const double*>(src), dp, total);
+            else hipLaunchKernelGGL(pack24_kernel<float>, g, b, 0, stream, static_cast<const float*>(src), dp, total);
+            return hipGetLastError();
+        }
+    }
     int64_t blocks = (n * C + 255) / 256;
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(convert_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, src, s_type, s_fs, s_cs,

@@ -20,7 +20,8 @@ struct SrcDesc {
     const void* in;
     int64_t in_base, in_len, in_fs, in_cs;
     int in_f64;
-    int in_pcm;            // 0 float input, else PCM bits (16: int16, 24/32: int32 storage) or 4 / 5: f16 / bf16
+    int in_pcm;            // 0 float input, else PCM bits (16: int16, 24/32: int32 storage), 280: packed 24-bit
+                           // (3 bytes per sample; in_fs / in_cs count samples) or 4 / 5: f16 / bf16
     int64_t valid_end;
 };
 
@@ -29,15 +30,19 @@ struct OutDesc {
     void* out;
     int64_t o0, fs, cs;
     int f64;
-    int pcm;               // 0 float output, else PCM bits (int(clamp(y, -1, 1) * maxVal)) or 4 / 5: f16 / bf16 (RNE)
+    int pcm;               // 0 float output, else PCM bits (int(clamp(y, -1, 1) * maxVal)), 280: packed 24-bit
+                           // (3 bytes per sample; fs / cs count samples) or 4 / 5: f16 / bf16 (RNE)
     int64_t o_lo, o_hi;
     int* err;              // the calling handle's device status word (host-mapped), null if none
 };
 
 // Integer PCM <-> float, after cmd/resample-wav/main.go:444-543 (maxInt16/24/32, main.go:54-56):
 // in = float64(i) * (1 / maxVal); out = int(clamp(float64(y), -1, 1) * maxVal), truncating.
+// Packed 24-bit PCM (gar.h GAR_PCM24_PACKED = 0x100 | 24) travels in the same fields under its ABI
+// code: GAR_PCM24's values in 3 bytes per sample, little-endian two's complement, at any byte address.
+constexpr int kSampPcm24P = 280;
 __host__ __device__ inline double pcmMax(int bits) {
-    return bits == 16 ? 32767.0 : (bits == 24 ? 8388607.0 : 2147483647.0);
+    return bits == 16 ? 32767.0 : ((bits == 24 || bits == kSampPcm24P) ? 8388607.0 : 2147483647.0);
 }
 // Half-precision samples (gar.h GAR_F16 / GAR_BF16) travel in the same fields as the PCM bits
 // (SrcDesc::in_pcm, OutDesc::pcm, launchConvert's type codes) under their ABI codes 4 and 5, below
@@ -71,15 +76,52 @@ __host__ __device__ inline float f32OddOfF64(double d) {
 }
 __host__ __device__ inline uint16_t halfOfF64(double d, int code) { return halfOfF32(f32OddOfF64(d), code); }
 
-__host__ __device__ inline int pcmBytes(int bits) { return bits <= 16 ? 2 : 4; }
+__host__ __device__ inline int pcmBytes(int bits) { return bits == kSampPcm24P ? 3 : (bits <= 16 ? 2 : 4); }
 __host__ __device__ inline double pcmToF64(int32_t i, int bits) { return static_cast<double>(i) * (1.0 / pcmMax(bits)); }
+// int(clamp(y, -1, 1) * maxVal), truncating; NaN passes the clamp as in Go and converts to 0
+__host__ __device__ inline int32_t pcmOfF64(double y, int bits) {
+    const double v = y > 1.0 ? 1.0 : (y < -1.0 ? -1.0 : y);
+    const double s = v * pcmMax(bits);
+    return s == s ? static_cast<int32_t>(s) : 0;
+}
+// One packed 24-bit sample at byte address b (no alignment): byte-wise, so nothing outside its 3 bytes is touched.
+__host__ __device__ inline int32_t pcm24Load(const uint8_t* b) {
+    const uint32_t u = static_cast<uint32_t>(b[0]) | (static_cast<uint32_t>(b[1]) << 8) | (static_cast<uint32_t>(b[2]) << 16);
+    return static_cast<int32_t>(u << 8) >> 8;  // sign-extend bit 23
+}
+__host__ __device__ inline void pcm24Store(uint8_t* b, int32_t i) {
+    b[0] = static_cast<uint8_t>(i);
+    b[1] = static_cast<uint8_t>(i >> 8);
+    b[2] = static_cast<uint8_t>(i >> 16);
+}
+// Four packed samples <-> three little-endian dwords (the vector pack / unpack kernels);
+// u32x3a: the three dwords as one 12-byte access from a 4-byte aligned address.
+typedef uint32_t u32x3a __attribute__((ext_vector_type(3), aligned(4)));
+__host__ __device__ inline void pcm24Pack4(const int32_t (&i)[4], uint32_t (&d)[3]) {
+    const uint32_t a = static_cast<uint32_t>(i[0]) & 0xffffffu, b = static_cast<uint32_t>(i[1]) & 0xffffffu;
+    const uint32_t c = static_cast<uint32_t>(i[2]) & 0xffffffu, e = static_cast<uint32_t>(i[3]) & 0xffffffu;
+    d[0] = a | (b << 24);
+    d[1] = (b >> 8) | (c << 16);
+    d[2] = (c >> 16) | (e << 8);
+}
+__host__ __device__ inline void pcm24Unpack4(const uint32_t (&d)[3], int32_t (&i)[4]) {
+    i[0] = static_cast<int32_t>(d[0] << 8) >> 8;
+    i[1] = static_cast<int32_t>(((d[0] >> 24) | (d[1] << 8)) << 8) >> 8;
+    i[2] = static_cast<int32_t>(((d[1] >> 16) | (d[2] << 16)) << 8) >> 8;
+    i[3] = static_cast<int32_t>(d[2]) >> 8;
+}
 __host__ __device__ inline double pcmRead(const void* p, int64_t e, int bits) {
     if (sampIsHalf(bits)) return static_cast<double>(halfToF32(static_cast<const uint16_t*>(p)[e], bits));
+    if (bits == kSampPcm24P) return pcmToF64(pcm24Load(static_cast<const uint8_t*>(p) + 3 * e), 24);
     return bits == 16 ? pcmToF64(static_cast<const int16_t*>(p)[e], 16) : pcmToF64(static_cast<const int32_t*>(p)[e], bits);
 }
 __host__ __device__ inline void pcmWrite(void* p, int64_t e, int bits, double y) {
     if (sampIsHalf(bits)) {
         static_cast<uint16_t*>(p)[e] = halfOfF64(y, bits);
+        return;
+    }
+    if (bits == kSampPcm24P) {
+        pcm24Store(static_cast<uint8_t*>(p) + 3 * e, pcmOfF64(y, 24));
         return;
     }
     const double v = y > 1.0 ? 1.0 : (y < -1.0 ? -1.0 : y);  // NaN passes through as in Go, then converts
@@ -203,8 +245,10 @@ hipError_t launchGather(int f64, const SrcDesc& src, void* dst, int64_t t0, int6
 // Strided copy with dtype conversion (pass-through stages, group split).
 hipError_t launchCopy(const void* src, int src_f64, int64_t s_fs, int64_t s_cs, void* dst, int dst_f64,
                       int64_t d_fs, int64_t d_cs, int64_t n, int C, hipStream_t stream);
-// PCM / half staging of the non-fused paths: type codes 0 f32, 1 f64, 4 f16, 5 bf16, 16/24/32 PCM
-// (pcmRead / pcmWrite); not the ABI's codes for f32 / f64.
+// PCM / half staging of the non-fused paths: type codes 0 f32, 1 f64, 4 f16, 5 bf16, 16/24/32 PCM, 280 packed
+// 24-bit (pcmRead / pcmWrite); not the ABI's codes for f32 / f64.  Packed 24-bit against a contiguous f32 / f64
+// buffer runs the vector kernels (unpack24_kernel / pack24_kernel: 4 samples <-> 3 dwords per thread) when the
+// packed side is interleaved-contiguous from a 4-byte aligned base; every other case the per-element kernel.
 hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs, void* dst, int d_type, int64_t d_fs,
                          int64_t d_cs, int64_t n, int C, hipStream_t stream);
 

@@ -91,6 +91,7 @@ EXPORTED = [
     "gar_status_string", "gar_last_error", "gar_design_engine", "gar_design_composite", "gar_profile_enable",
     "gar_profile_read", "gar_stage_state", "gar_num_stages", "gar_stage_geometry", "gar_get_statistics",
     "gar_synchronize", "gar_profile_launch_stats", "gar_profile_kinds", "gar_dev_half_convert",
+    "gar_dev_pcm24_convert",
 ]
 
 _lib = None
@@ -156,6 +157,7 @@ def lib():
         "gar_profile_kinds": (None, [vp, C.c_uint32]),
         "gar_profile_launch_stats": (i32, [vp, i32, C.POINTER(d), C.POINTER(d), C.POINTER(d)]),
         "gar_dev_half_convert": (i32, [i32, vp, i64, vp, vp, vp]),
+        "gar_dev_pcm24_convert": (i32, [vp, i64, vp, vp]),
     }
     ab = os.environ.get("GAR_LIB_PATH") is not None
     for name, (res, args) in sig.items():
@@ -355,9 +357,15 @@ class Resampler:
         cmd/resample-wav/main.go:444-543 (input i * (1/maxVal), output int(clamp(y, -1, 1) * maxVal)).
         float16 / bfloat16 samples are widened exactly on input and rounded once, to nearest even, on
         output (overflow gives +-Inf, no clamp; gar.h GAR_F16 / GAR_BF16).
+        Packed 24-bit PCM (gar.h GAR_PCM24_PACKED, the 3-byte little-endian samples of a 24-bit WAV) is a
+        uint8 tensor [frames, channels, 3]: last stride 1, the other strides multiples of 3, any base
+        address; values are PCM24's.  An output allocated here has x's form.
         x.shape[1] (and out.shape[1]) must equal Channels (ErrChannelMismatch)."""
         import torch
-        assert x.is_cuda and x.dim() == 2
+        _check_form(x)
+        if out is not None:
+            _check_form(out)
+        assert x.is_cuda
         if x.shape[1] != self.Channels or (out is not None and out.shape[1] != self.Channels):
             raise ErrChannelMismatch(f"expected {self.Channels} channels, got {x.shape[1]}"
                                      + ("" if out is None else f" (out {out.shape[1]})"))
@@ -366,42 +374,52 @@ class Resampler:
         if n < 0:
             raise ErrNotSupported("channels not in lockstep")
         if out is None:
-            out = torch.empty((max(n, 1), x.shape[1]), dtype=x.dtype, device=x.device)
+            out = torch.empty((max(n, 1),) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
         got = C.c_int64(0)
         dt = _io_type(x.dtype, pcm_bits)
         odt = _io_type(out.dtype, pcm_bits)
+        (xfs, xcs), (ofs, ocs) = _sample_strides(x), _sample_strides(out)
         st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream)
-        _check(lib().gar_process_device(self._h, C.c_void_p(x.data_ptr()), dt, x.stride(0), x.stride(1), frames,
-                                        x.shape[1], C.c_void_p(out.data_ptr()), odt, out.stride(0), out.stride(1),
+        _check(lib().gar_process_device(self._h, C.c_void_p(x.data_ptr()), dt, xfs, xcs, frames,
+                                        x.shape[1], C.c_void_p(out.data_ptr()), odt, ofs, ocs,
                                         out.shape[0], C.byref(got), st))
         return out[: got.value]
 
     def flush_device(self, out=None, dtype=None, stream=None, pcm_bits=None):
         """Flush all channels into a device tensor (FlushMulti semantics): `out`, or a new tensor of
-        `dtype` (default float32; any sample type process_device takes, float16 / bfloat16 included)."""
+        `dtype` (default float32; any sample type process_device takes, float16 / bfloat16 included;
+        torch.uint8 allocates packed 24-bit PCM, [frames, channels, 3])."""
         import torch
+        if out is not None:
+            _check_form(out)
         if out is not None and out.shape[1] != self.Channels:
             raise ErrChannelMismatch(f"expected {self.Channels} channels, got {out.shape[1]}")
         n = lib().gar_device_flush_size(self._h)
         if n < 0:
             raise ErrNotSupported("channels not in lockstep")
         if out is None:
-            out = torch.empty((max(n, 1), self.Channels), dtype=dtype or torch.float32, device="cuda")
+            shape = (max(n, 1), self.Channels) + ((3,) if dtype == torch.uint8 else ())
+            out = torch.empty(shape, dtype=dtype or torch.float32, device="cuda")
         got = C.c_int64(0)
         odt = _io_type(out.dtype, pcm_bits)
+        ofs, ocs = _sample_strides(out)
         st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(out.device).cuda_stream)
-        _check(lib().gar_flush_device(self._h, out.shape[1], C.c_void_p(out.data_ptr()), odt, out.stride(0),
-                                      out.stride(1), out.shape[0], C.byref(got), st))
+        _check(lib().gar_flush_device(self._h, out.shape[1], C.c_void_p(out.data_ptr()), odt, ofs,
+                                      ocs, out.shape[0], C.byref(got), st))
         return out[: got.value]
 
 
 PCM16, PCM24, PCM32 = 16, 24, 32
 F16, BF16 = 4, 5  # device sample types only (gar.h GAR_F16 / GAR_BF16), not compute types
+PCM24_PACKED = 280  # device sample type only (gar.h GAR_PCM24_PACKED): 3 bytes per sample, little-endian
 
 
 def _io_type(dtype, pcm_bits=None):
-    """Device sample type code of a torch dtype (gar.h GAR_F32/GAR_F64/GAR_F16/GAR_BF16/GAR_PCM*)."""
+    """Device sample type code of a torch dtype (gar.h GAR_F32/GAR_F64/GAR_F16/GAR_BF16/GAR_PCM*);
+    uint8 is packed 24-bit PCM (tensors of shape [frames, channels, 3])."""
     import torch
+    if dtype == torch.uint8:
+        return PCM24_PACKED
     if dtype == torch.float64:
         return F64
     if dtype == torch.float32:
@@ -418,6 +436,53 @@ def _io_type(dtype, pcm_bits=None):
             raise ValueError("int32 PCM holds 24- or 32-bit samples")
         return bits
     raise TypeError(f"unsupported sample dtype {dtype}")
+
+
+def _check_form(t):
+    """A device sample tensor is [frames, channels], or for packed 24-bit PCM (uint8) [frames, channels, 3]
+    with the 3 bytes of a sample adjacent and the other strides whole samples."""
+    import torch
+    if t.dtype == torch.uint8:
+        if t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError(f"packed 24-bit PCM is a uint8 tensor [frames, channels, 3], got shape {tuple(t.shape)}")
+        if t.stride(2) != 1 or t.stride(0) % 3 or t.stride(1) % 3:
+            raise ValueError(f"packed 24-bit PCM needs strides (3 a, 3 b, 1), got {tuple(t.stride())}")
+    elif t.dim() != 2:
+        raise ValueError(f"sample tensors are [frames, channels], got shape {tuple(t.shape)}")
+
+
+def _sample_strides(t):
+    """(frame_stride, channel_stride) in samples (units of 3 bytes for packed 24-bit PCM)."""
+    if t.dim() == 3:
+        return t.stride(0) // 3, t.stride(1) // 3
+    return t.stride(0), t.stride(1)
+
+
+def pack_pcm24(i):
+    """int32 samples (numpy array or tensor, any shape) -> uint8 [..., 3]: the low three bytes of each,
+    little-endian (the layout of GAR_PCM24_PACKED and of 24-bit WAV data).  Host, numpy."""
+    a = np.ascontiguousarray(i.cpu().numpy() if hasattr(i, "cpu") else i).astype(np.int32)
+    u = a.astype(np.uint32)
+    return np.stack([(u & 0xFF), ((u >> 8) & 0xFF), ((u >> 16) & 0xFF)], axis=-1).astype(np.uint8)
+
+
+def unpack_pcm24(b):
+    """uint8 [..., 3] packed 24-bit samples (numpy array or tensor) -> sign-extended int32 [...].  Host, numpy."""
+    a = np.asarray(b.cpu().numpy() if hasattr(b, "cpu") else b, dtype=np.uint8)
+    if a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError(f"packed 24-bit samples have a last dimension of 3, got shape {a.shape}")
+    u = a[..., 0].astype(np.uint32) | (a[..., 1].astype(np.uint32) << 8) | (a[..., 2].astype(np.uint32) << 16)
+    return ((u << 8).astype(np.int32) >> 8).astype(np.int32)
+
+
+def pcm24_convert(x):
+    """Host run of the kernels' packed 24-bit conversions (gar.h gar_dev_pcm24_convert) on the float64
+    array x: (uint8 [n, 3] bytes a float64-compute handle stores, those bytes read back as int32)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    b = np.zeros((x.size, 3), dtype=np.uint8)
+    i = np.zeros(x.size, dtype=np.int32)
+    _check(lib().gar_dev_pcm24_convert(_p(x), x.size, _p(b), _p(i)))
+    return b, i
 
 
 def half_convert(x, half_type):

@@ -75,6 +75,24 @@ enum { GAR_PCM16 = 16, GAR_PCM24 = 24, GAR_PCM32 = 32 };
  * Fused into the split-f16 kernel's loads and stores wherever PCM is (a stereo frame is one dword,
  * like a PCM16 frame); staged through the conversion kernel otherwise. */
 enum { GAR_F16 = 4, GAR_BF16 = 5 };
+/* packed 24-bit PCM, the layout of 24-bit WAV data (cmd/resample-wav/main.go:648-665 WriteSamples24:
+ * byte(s), byte(s>>8), byte(s>>16)): a sample type of the device entry points only (in_dtype /
+ * out_dtype of gar_process_device and gar_flush_device; input and output types stay independent:
+ * packed in / f32 out, PCM16 in / packed out, f16 in / packed out are all legal).  As compute_dtype
+ * gar_config_validate, gar_new and gar_new_batch answer GAR_ERR_INVALID_CONFIG.
+ *   layout: 3 bytes per sample, little-endian, two's complement.  frame_stride and channel_stride
+ *           count SAMPLES, i.e. units of 3 bytes: sample (t, c) occupies the bytes
+ *           base + 3 * (t * frame_stride + c * channel_stride) + {0, 1, 2}.  The base pointer needs
+ *           no alignment (the vector conversion kernels take a 4-byte aligned base of an interleaved
+ *           contiguous buffer; any other base or layout runs the byte-wise kernel, same results).
+ *   values: exactly GAR_PCM24's.  In: the 3 bytes sign-extended, then float64(i) * (1 / 8388607).
+ *           Out: int(clamp(y, -1, 1) * 8388607), truncating, NaN -> 0; its low three bytes stored.
+ *   bounds: no call reads or writes a byte outside the frames x channels samples the strides
+ *           describe -- no vector load reaches past the last frame, no store touches the byte
+ *           after a sample (or the gap bytes of a strided layout).
+ * Always staged through the pack / unpack kernels around the float path (not fused into the FIR
+ * kernel's loads and stores). */
+enum { GAR_PCM24_PACKED = 0x100 | 24 };
 /* engine.Quality (internal/engine/filter_params.go:16-41), for gar_design_engine */
 enum { GAR_ENGINE_QUICK = 0, GAR_ENGINE_LOW, GAR_ENGINE_MEDIUM, GAR_ENGINE_HIGH, GAR_ENGINE_VERYHIGH,
        GAR_ENGINE_16BIT, GAR_ENGINE_20BIT, GAR_ENGINE_24BIT, GAR_ENGINE_28BIT, GAR_ENGINE_32BIT };
@@ -261,6 +279,12 @@ int64_t gar_dev_pool_selftest(int32_t threads, int32_t iters, int32_t channels, 
  * conversion).  Any output may be NULL.  For tests (CPU suite). */
 gar_status gar_dev_half_convert(int32_t half_type, const double *in, int64_t n, uint16_t *from_f64,
                                 uint16_t *from_f32, float *widened);
+
+/* The sample conversions of GAR_PCM24_PACKED run on the host (no GPU; the kernels use the same
+ * functions): packed[3 i .. 3 i + 2] = the 3 bytes a float64-compute handle stores for in[i],
+ * unpacked[i] = those bytes read back as the sign-extended integer (the input conversion before
+ * its scaling).  Either output may be NULL.  For tests (CPU suite). */
+gar_status gar_dev_pcm24_convert(const double *in, int64_t n, uint8_t *packed, int32_t *unpacked);
 
 /* ---- host-only design introspection (no GPU needed) ----------------------- */
 typedef struct gar_engine_geometry {

@@ -16,6 +16,7 @@
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -28,6 +29,7 @@
 
 #include "gar.h"
 #include "gar_design.hpp"
+#include "gar_hxs_launch.hpp"
 #include "gar_kernels.hpp"
 #include "gar_plan.hpp"
 #include "gar_pool.hpp"
@@ -2123,6 +2125,40 @@ gar_status gar_dev_pcm24_convert(const double* in, int64_t n, uint8_t* packed, i
         if (packed) std::memcpy(packed + 3 * i, b, 3);
         if (unpacked) unpacked[i] = pcm24Load(b);
     }
+    return GAR_OK;
+}
+
+gar_status gar_dev_hxs_plan(const gar_resampler* r, int32_t stage, int32_t in_type, int64_t in_fs, int64_t in_cs,
+                            uint64_t in_addr, int64_t in_base, int64_t in_len, int64_t valid_end, uint64_t hist_addr,
+                            int64_t hist_len, int64_t hist_ld, int32_t out_type, uint64_t out_addr, int64_t o0,
+                            int64_t out_fs, int64_t out_cs, int64_t o_lo, int64_t o_hi, int32_t channels,
+                            int32_t cu_count, int64_t hist_keep, char* buf, int64_t cap) {
+    if (!r || !buf || cap < 1 || stage < 0 || stage >= static_cast<int32_t>(r->stages.size()) || channels < 1 ||
+        cu_count < 1 || !ioTypeOk(in_type) || !ioTypeOk(out_type))
+        return guard(GAR_ERR_INVALID_ARGUMENT, "bad launch-plan arguments");
+    const gar::StageRT& st = *r->stages[stage];
+    const HxDev* hx = st.fusedD.hx ? st.fusedD.hx : (st.dftD.hx ? st.dftD.hx : st.decimD.hx);
+    if (!hx) return guard(GAR_ERR_INVALID_ARGUMENT, "the stage has no split-f16 plan");
+    SrcDesc src{};
+    src.hist = reinterpret_cast<const void*>(static_cast<uintptr_t>(hist_addr));
+    src.hist_len = hist_len;
+    src.hist_ld = hist_ld;
+    src.in = reinterpret_cast<const void*>(static_cast<uintptr_t>(in_addr));
+    src.in_base = in_base; src.in_len = in_len; src.in_fs = in_fs; src.in_cs = in_cs;
+    src.in_f64 = in_type == GAR_F64;
+    src.in_pcm = isNarrow(in_type) ? in_type : 0;
+    src.valid_end = valid_end;
+    OutDesc od{};
+    od.out = reinterpret_cast<void*>(static_cast<uintptr_t>(out_addr));
+    od.o0 = o0; od.fs = out_fs; od.cs = out_cs;
+    od.f64 = out_type == GAR_F64;
+    od.pcm = isNarrow(out_type) ? out_type : 0;
+    od.o_lo = o_lo; od.o_hi = o_hi;
+    buf[0] = 0;
+    if (o_hi <= o_lo) return GAR_OK;  // launchHxs: nothing to launch
+    const gar::HxsLaunchPlan pl = gar::hxsPlanLaunch(*hx, src, od, channels, cu_count, gar::hxsReadKnobs(), hist_keep > 0, hist_keep);
+    if (!pl.ok) std::snprintf(buf, static_cast<size_t>(cap), "not supported\n");
+    else gar::hxsTraceLines(pl, od, channels, buf, static_cast<size_t>(cap));
     return GAR_OK;
 }
 

@@ -31,9 +31,6 @@ hipError_t hxDispatch(const HxArgs& x, int waves, size_t lds, int64_t blocks, in
     }
 }
 
-int64_t floorDiv(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-int64_t ceilDiv(int64_t a, int64_t b) { return -floorDiv(-a, b); }
-
 }  // namespace
 
 hipError_t launchHx(const HxDev& p, const SrcDesc& src, const OutDesc& od, int C, hipStream_t stream, HistCopy* hc) {

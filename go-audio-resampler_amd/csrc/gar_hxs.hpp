@@ -28,33 +28,15 @@
 #include <climits>
 
 #include "gar_hx.hpp"
+#include "gar_hxs_geo.hpp"
 
 namespace gar {
 
-#ifndef GAR_HXS_L
-#define GAR_HXS_L 6
-#endif
-constexpr int kHxsLoaders = GAR_HXS_L;                  // loader waves per workgroup
-constexpr int kHxsWaves = kHxRbMaxWaves + kHxsLoaders;  // __launch_bounds__ (4 waves per SIMD, 128 VGPRs)
 #ifndef GAR_HXS_D
 #define GAR_HXS_D 2
 #endif
 constexpr int kHxsD = GAR_HXS_D;                        // loads in flight per loader wave (register staging)
-#ifndef GAR_HXS_NP
-#define GAR_HXS_NP 12
-#endif
-constexpr int kHxsNP = GAR_HXS_NP;                      // 64-row pieces per load (G*Qc <= 768: cfg2 G = 5)
-constexpr int kHxsMaxG = 6;                             // periods per group (launcher: largest that fits)
 constexpr int kHxsItems = (4 * kHxsNP + kHxsLoaders - 1) / kHxsLoaders;  // (quad, piece) items per loader per load
-// Development instrumentation (GAR_HXS_DBG attribution modes, GAR_HXS_PROF phase cycles): compiled
-// in only with -DGAR_HXS_DEV=1 (tools/hxs_variant.sh); the production kernel carries none of it.
-#ifndef GAR_HXS_DEV
-#define GAR_HXS_DEV 0
-#endif
-constexpr bool kHxsDev = GAR_HXS_DEV != 0;
-#ifndef GAR_HXS_QUICK
-#define GAR_HXS_QUICK 0
-#endif
 #ifndef GAR_HXS_PRIO
 #define GAR_HXS_PRIO 0
 #endif

@@ -26,13 +26,6 @@
 
 namespace gar {
 
-// NL loader waves (template parameter, 4 or 6) + up to 16 - NL compute waves, 16 waves at most.
-constexpr int kHxtMaxComp = 12;                         // compute waves (3 per SIMD)
-constexpr int kHxtWaves = 16;                           // __launch_bounds__: 16 waves, 128 VGPRs
-constexpr int kHxtD = 2;                                // loads in flight per loader (register staging)
-// 64-row pieces of one load (G*Qc <= 64 * pieces): 10 with 4 loaders, 12 with 6 (the registers
-// of a loader's two loads in flight stay at 80 / 64 VGPRs)
-__host__ __device__ constexpr int hxtPieces(int NL) { return NL >= 6 ? 12 : 10; }
 __host__ __device__ constexpr int hxtMaxRows(int NL) { return 64 * hxtPieces(NL); }
 // Items of loader l (of NL): FMT 1 item it = l + NL*k covers quad it & 3, 64-row piece it >> 2;
 // FMT 2 item it = l + NL*k is the 16-row piece it (all four quads, lane = 16 quad + row);
@@ -46,9 +39,6 @@ constexpr int hxtItems() { return (4 * hxtPieces(NL) + NL - 1) / NL; }
 // ring of eight quads; each compute wave runs both tiles of its row block per period.
 __host__ __device__ constexpr int hxtQuads(int FMT) { return FMT == 5 ? 8 : 4; }
 __host__ __device__ constexpr int hxtCols(int FMT) { return 4 * hxtQuads(FMT); }
-__host__ __device__ constexpr int hxtMaxRowsF(int FMT, int NL) {
-    return FMT == 5 ? 8 * NL * ((4 * hxtPieces(NL) + NL - 1) / NL) : 64 * hxtPieces(NL);
-}
 // loader waves' issue priority (s_setprio; 0 = the compute waves' level).  The loaders share each
 // SIMD with three MFMA-issuing compute waves; at equal priority the arbiter lets the MFMA stream
 // starve the loaders' VALU (r05 stamps: ~19 cycles per loader VALU instruction), and the loaders
@@ -346,7 +336,6 @@ __device__ __forceinline__ void hxtConvert(const HxsArgs& x, const HxsStage& st,
 // drains) and in the handle's device status word x.err (host-mapped; the C-ABI reports
 // GAR_ERR_DEVICE naming hxt_kernel and refuses the handle until Reset) -- never silent output.
 typedef __attribute__((address_space(3))) int lds_i32;
-constexpr int kHxtSlots = 16;                            // arrival slots per direction
 // Explicit LDS pointers: a generic pointer makes the polls flat loads, and a flat load's
 // s_waitcnt vmcnt(0) waits for every store the wave has in flight.
 struct HxtSync {
@@ -354,11 +343,8 @@ struct HxtSync {
     lds_i32* cpArr;   // [kHxtSlots] compute-wave arrivals per group
     lds_i32* abort;   // a wait of this workgroup expired (sticky for the launch)
 };
-// LDS bytes past loudLo (hxsLds reserves them): loudLo[16], loudHi[16], flag, then the counters
-// (FMT 5: loudLo[32], loudHi[32], flag)
-constexpr int kHxtSyncOff = 160;
-__host__ __device__ constexpr int hxtSyncOff(int FMT) { return FMT == 5 ? 288 : kHxtSyncOff; }
-constexpr int kHxtSyncBytes = 4 * (2 * kHxtSlots + 1);
+// LDS bytes past loudLo of the counters (gar_hxs_geo.hpp)
+__host__ __device__ constexpr int hxtSyncOff(int FMT) { return FMT == kFmtRow32 ? kHxtSyncOffWide : kHxtSyncOff; }
 
 // Producer arrival for item j.
 __device__ __forceinline__ void hxtArrive(lds_i32* arr, int j, int lane) {
@@ -577,23 +563,6 @@ __device__ __forceinline__ void hxtLoaders(const HxsArgs& x, const HxsShared& sh
 // Same loads, same split, same loud test (running max, exact re-gather when it fires), same ring
 // image: the compute waves and the bits do not change.  Loads before the steady state (history
 // seam, stream start) stay with hxtLoaders, which stops at the step the lean loop starts from.
-template <int QC, int G_, int KREAD>
-struct HxtGeo {  // hxsRingFor's geometry (gar_hxs.hip) as constants; the launcher dispatches on an exact match
-    static constexpr int Qc = QC, G = G_, GQ = G_ * QC, Wg = (G_ - 1) * QC + KREAD;
-    static constexpr int nslot = (Wg + GQ + GQ - 1) / GQ, R = nslot * GQ;
-    static constexpr int mirror = Wg > GQ ? Wg - GQ : 0;
-    static constexpr int Rt = (R + mirror + 15) / 16 * 16;
-    static constexpr int P = (Wg + GQ - 1) / GQ;
-    static constexpr uint32_t QS = 16u * Rt + 64u, dL = 8u * Rt;
-    // first step (j - P) whose ring rows had an occupant, hxtFreeNeed: step i waits for group i - i0
-    static constexpr int i0 = (R + 1 - Wg + GQ - 1) / GQ - 1;
-    static_assert(Wg > GQ && mirror < GQ && P % kHxtD == 0 && i0 >= 0, "lean loaders: ring shape");
-};
-// Q24 44.1k -> 48k (Qc 147, Kread 420): G = 5 beside six loaders, G = 4 beside four (balanced roles)
-template <int NL>
-using HxtLeanGeo = HxtGeo<147, NL >= 6 ? 5 : 4, 420>;
-constexpr int kHxtLeanPc = 160, kHxtLeanNS = 9;
-
 // Item k of loader l: quad qL(l) + q(k), 64-row piece pcL(l) + pcS(k).
 template <int NL>
 struct HxtLeanMap;

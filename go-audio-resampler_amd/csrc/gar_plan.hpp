@@ -19,6 +19,10 @@
 
 namespace gar {
 
+// floor / ceiling of a / b for b > 0 and any sign of a (launch geometry: outputs -> macro periods)
+inline int64_t floorDiv(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+inline int64_t ceilDiv(int64_t a, int64_t b) { return -floorDiv(-a, b); }
+
 struct FirPeriodic {
     int P = 0, Q = 0;                 // outputs / inputs per period
     std::vector<int64_t> off;         // [P] input offset of output r within the period

@@ -286,6 +286,25 @@ gar_status gar_dev_half_convert(int32_t half_type, const double *in, int64_t n, 
  * its scaling).  Either output may be NULL.  For tests (CPU suite). */
 gar_status gar_dev_pcm24_convert(const double *in, int64_t n, uint8_t *packed, int32_t *unpacked);
 
+/* The launch plan of the streaming FIR kernels for one call, computed on the host (no GPU; the
+ * planner launchHxs runs, csrc/gar_hxs_launch.hpp): writes the GAR_HX_TRACE line(s) such a launch
+ * prints -- kernel, group size, chunking, ring, load / store layout, raw-load rows, compute waves,
+ * loaders -- into buf (NUL-terminated, at most cap bytes), "not supported\n" when the planner
+ * declines, nothing for an empty output range.  `r` may be a dry-run handle; `stage` picks the
+ * pipeline stage, whose split-f16 plan is taken (fused, else DFT, else decimator;
+ * GAR_ERR_INVALID_ARGUMENT if it has none).  Types are the ABI's sample type codes; addresses are
+ * used as integers (alignment, base offsets) and never dereferenced.  Source: element (t, c) of the
+ * new input at in_addr + ((t - in_base) * in_fs + c * in_cs) elements for t in [in_base, in_base +
+ * in_len), zeros from valid_end, in_addr 0 for a flush; history rows of stride hist_ld at hist_addr.
+ * Output: element (o, c) at out_addr + ((o - o0) * out_fs + c * out_cs) elements, o in [o_lo, o_hi).
+ * hist_keep: rows of a history keep folded into the launch (0: none).  The knobs are read
+ * from the environment on every call.  For tests (CPU suite). */
+gar_status gar_dev_hxs_plan(const gar_resampler *r, int32_t stage, int32_t in_type, int64_t in_fs, int64_t in_cs,
+                            uint64_t in_addr, int64_t in_base, int64_t in_len, int64_t valid_end, uint64_t hist_addr,
+                            int64_t hist_len, int64_t hist_ld, int32_t out_type, uint64_t out_addr, int64_t o0,
+                            int64_t out_fs, int64_t out_cs, int64_t o_lo, int64_t o_hi, int32_t channels,
+                            int32_t cu_count, int64_t hist_keep, char *buf, int64_t cap);
+
 /* ---- host-only design introspection (no GPU needed) ----------------------- */
 typedef struct gar_engine_geometry {
     int32_t kind; /* 0 cubic, 1 DFT-only, 2 DFT x2 + polyphase, 3 decimator, 4 pass-through */

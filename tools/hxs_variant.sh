@@ -13,6 +13,11 @@ units=${UNITS:-"gar_hxs gar_hxs_i1 gar_hxs_i2 gar_hxt_i1 gar_hxt_i2"}
 for f in $units; do
   /opt/rocm/bin/hipcc $CXXFLAGS $flags --offload-arch=gfx950 -c csrc/$f.hip -o build/$name/$f.o &
 done
+# the launcher's host-only planner shares the kernels' build-time constants (csrc/gar_hxs_geo.hpp)
+case " $units " in *" gar_hxs "*)
+  units="$units gar_hxs_launch"
+  /opt/rocm/bin/hipcc $CXXFLAGS $flags -x c++ -D__HIP_PLATFORM_AMD__ -c csrc/gar_hxs_launch.cpp -o build/$name/gar_hxs_launch.o & ;;
+esac
 wait
 objs=$(for o in build/*.o; do b=$(basename $o .o); case " $units " in *" $b "*) ;; *) echo $o;; esac; done)
 /opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -o libgar_$name.so $objs build/$name/*.o

@@ -739,4 +739,55 @@ hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// State snapshots (StateSeg, gar_kernels.hpp): thread g takes 16-byte chunk g of the table's chunk
+// numbering -- the segment whose chunk0 is the last one <= g (binary search; chunk0 strictly increases),
+// chunk g - chunk0 of it.  PACK: history -> image, else image -> history.
+template <bool PACK>
+__global__ __launch_bounds__(256) void state_copy_kernel(const StateSeg* segs, int nseg, int64_t nchunks, char* img) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    for (int64_t g = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; g < nchunks;
+         g += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        int lo = 0, hi = nseg - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (segs[mid].chunk0 <= g) lo = mid; else hi = mid - 1;
+        }
+        const StateSeg s = segs[lo];
+        const int64_t bytes = s.rows * s.C * s.es;
+        const int64_t b = (g - s.chunk0) * 16;
+        if (b < 0 || b >= bytes) continue;  // not a chunk of this segment (a table that is not as specified)
+        char* hp = static_cast<char*>(s.ptr) + b;
+        char* ip = img + s.off + b;
+        const char* src = PACK ? hp : ip;
+        char* dst = PACK ? ip : hp;
+        if (b + 16 <= bytes && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+            *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
+        } else {  // a segment's tail (or an unaligned side): whole elements up to the segment's end
+            const int64_t e = (b + 16 < bytes ? b + 16 : bytes) - b;
+            if (s.es == 8) {
+                for (int64_t o = 0; o + 8 <= e; o += 8) *reinterpret_cast<uint64_t*>(dst + o) = *reinterpret_cast<const uint64_t*>(src + o);
+            } else {
+                for (int64_t o = 0; o + 4 <= e; o += 4) *reinterpret_cast<uint32_t*>(dst + o) = *reinterpret_cast<const uint32_t*>(src + o);
+            }
+        }
+    }
+}
+
+template <bool PACK>
+static hipError_t stateCopy(const StateSeg* segs, int nseg, int64_t nchunks, char* img, hipStream_t stream) {
+    if (nseg <= 0 || nchunks <= 0) return hipSuccess;
+    int64_t blocks = (nchunks + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(state_copy_kernel<PACK>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, segs, nseg, nchunks, img);
+    return hipGetLastError();
+}
+
+hipError_t launchStatePack(const StateSeg* segs, int nseg, int64_t nchunks, void* img, hipStream_t stream) {
+    return stateCopy<true>(segs, nseg, nchunks, static_cast<char*>(img), stream);
+}
+hipError_t launchStateUnpack(const StateSeg* segs, int nseg, int64_t nchunks, const void* img, hipStream_t stream) {
+    return stateCopy<false>(segs, nseg, nchunks, const_cast<char*>(static_cast<const char*>(img)), stream);
+}
+
 }  // namespace gar

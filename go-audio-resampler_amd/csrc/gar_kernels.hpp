@@ -252,4 +252,24 @@ hipError_t launchCopy(const void* src, int src_f64, int64_t s_fs, int64_t s_cs, 
 hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs, void* dst, int d_type, int64_t d_fs,
                          int64_t d_cs, int64_t n, int C, hipStream_t stream);
 
+// One history of a state snapshot (gar_state_save / gar_state_load): `rows` rows of C elements of `es`
+// bytes, contiguous at `ptr` (leading dimension C, the engine's Hist layout), stored tightly packed from
+// byte `off` (a multiple of 16) of the snapshot's row image.  chunk0 = 16-byte chunks of the segments
+// before this one in the table (each segment has ceil(rows * C * es / 16)); no segment is empty.
+struct StateSeg {
+    void* ptr;
+    int64_t rows;
+    int32_t C, es;
+    int64_t off;
+    int64_t chunk0;
+};
+// Every segment of a handle in ONE launch: pack gathers the histories into the contiguous device image
+// `img` (then one device-to-host copy), unpack scatters an uploaded image into the histories.  `segs`
+// is the table in device memory (nseg entries, nchunks chunks in all).  Work is spread over (segment,
+// 16-byte chunk): one 16-byte load + store where the chunk is whole and both sides are 16-byte aligned,
+// element by element otherwise (a segment's tail), so nothing past a segment's last row is touched.
+// The pad bytes between segments of the image are neither read nor written.
+hipError_t launchStatePack(const StateSeg* segs, int nseg, int64_t nchunks, void* img, hipStream_t stream);
+hipError_t launchStateUnpack(const StateSeg* segs, int nseg, int64_t nchunks, const void* img, hipStream_t stream);
+
 }  // namespace gar

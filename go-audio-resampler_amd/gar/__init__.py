@@ -91,7 +91,7 @@ EXPORTED = [
     "gar_status_string", "gar_last_error", "gar_design_engine", "gar_design_composite", "gar_profile_enable",
     "gar_profile_read", "gar_stage_state", "gar_num_stages", "gar_stage_geometry", "gar_get_statistics",
     "gar_synchronize", "gar_profile_launch_stats", "gar_profile_kinds", "gar_dev_half_convert",
-    "gar_dev_pcm24_convert", "gar_dev_hxs_plan",
+    "gar_dev_pcm24_convert", "gar_dev_hxs_plan", "gar_state_size", "gar_state_save", "gar_state_load",
 ]
 
 _lib = None
@@ -160,6 +160,9 @@ def lib():
         "gar_dev_pcm24_convert": (i32, [vp, i64, vp, vp]),
         "gar_dev_hxs_plan": (i32, [vp, i32, i32, i64, i64, C.c_uint64, i64, i64, i64, C.c_uint64, i64, i64, i32, C.c_uint64,
                                    i64, i64, i64, i64, i64, i32, i32, i64, C.c_char_p, i64]),
+        "gar_state_size": (i64, [vp]),
+        "gar_state_save": (i32, [vp, vp, i64, C.POINTER(i64)]),
+        "gar_state_load": (i32, [vp, vp, i64]),
     }
     ab = os.environ.get("GAR_LIB_PATH") is not None
     for name, (res, args) in sig.items():
@@ -176,7 +179,9 @@ def lib():
 def _check(rc):
     if rc != GAR_OK:
         msg = lib().gar_last_error().decode(errors="replace")
-        raise _ERRS.get(rc, ResamplerError)(msg or lib().gar_status_string(rc).decode())
+        err = _ERRS.get(rc, ResamplerError)(msg or lib().gar_status_string(rc).decode())
+        err.code = rc  # the plain ResamplerError of a status without a class of its own carries it too
+        raise err
 
 
 def _p(a):
@@ -331,6 +336,32 @@ class Resampler:
         """Wait for the handle's enqueued device work; raises ResamplerError (GAR_ERR_DEVICE) when a
         kernel reported a broken invariant (gar.h gar_synchronize)."""
         _check(lib().gar_synchronize(self._h))
+
+    # -- state snapshots (gar.h gar_state_size / gar_state_save / gar_state_load) --
+    def state_size(self):
+        """Bytes save_state() would return now."""
+        return lib().gar_state_size(self._h)
+
+    def save_state(self, cap=None):
+        """The handle's streaming state (groups, counters, histories, statistics) as bytes, after every
+        enqueued call has run.  `cap` (default: state_size()) is the buffer offered; one too small
+        raises ErrBufferTooSmall whose `needed` attribute is the size required."""
+        cap = self.state_size() if cap is None else int(cap)
+        buf = (C.c_ubyte * max(cap, 1))()
+        got = C.c_int64(0)
+        try:
+            _check(lib().gar_state_save(self._h, buf, cap, C.byref(got)))
+        except ErrBufferTooSmall as e:
+            e.needed = got.value
+            raise
+        return bytes(memoryview(buf)[: got.value])
+
+    def load_state(self, blob):
+        """Replace the handle's streaming state with a save_state() blob of a handle constructed with
+        the same arguments; anything else raises ResamplerError (code INVALID_ARGUMENT) and changes
+        nothing."""
+        blob = bytes(blob)
+        _check(lib().gar_state_load(self._h, blob, len(blob)))
 
     def num_stages(self):
         return lib().gar_num_stages(self._h)

@@ -232,6 +232,44 @@ int64_t gar_device_flush_size(const gar_resampler *r);
  * is the synchronisation point of the asynchronous *_device entry points. */
 gar_status gar_synchronize(gar_resampler *r);
 
+/* ---- state snapshots (checkpoint / resume / migrate) ---------------------- */
+/* The streaming state of a handle -- every channel group with its channel range, the per-stage
+ * counters (history lengths, polyphase position, decimator phase, cubic phase, fused / stage-by-stage
+ * mode), the history rows themselves and the GetStatistics counters -- as one self-contained blob in
+ * HOST memory.  No Go counterpart: the reference's state lives in the caller's process; an engine
+ * behind a C ABI has to hand it out itself.  The design (filter banks, launch plans) is not in the
+ * blob: a blob is loaded into a handle constructed with the same arguments, whose own design is used.
+ * A blob is little-endian and versioned (layout: DESIGN.md "State snapshots"); it serves checkpoints
+ * and migration between builds of the same version, and another version is refused.  One state has
+ * exactly one blob: save -> load -> save gives identical bytes.
+ *
+ * gar_state_size: bytes gar_state_save would write now (host bookkeeping only, no wait); -1 for NULL.
+ *
+ * gar_state_save: waits for every call enqueued on the handle, on any stream (the wait of
+ * gar_synchronize), then writes the snapshot into buf[0:*n_written].  cap smaller than the snapshot:
+ * GAR_ERR_BUFFER_TOO_SMALL, *n_written = the size needed, nothing written.  A handle that refuses
+ * work after a device error, or whose device status word is raised: GAR_ERR_DEVICE.  Saving does not
+ * change the handle: the next call's output is bit-identical with or without it.  n_written may be
+ * NULL.  On a real handle the rows are gathered by one kernel launch and fetched by one copy.
+ *
+ * gar_state_load: replaces the handle's streaming state with the blob's -- groups and channel ranges
+ * (a handle split by per-channel host calls comes back split), counters, histories, statistics.
+ * Synchronous: it waits for the handle's enqueued calls first, buf may be freed on return, and later
+ * calls on any stream are ordered after it.  The blob is treated as untrusted input and checked in
+ * full before anything changes; GAR_ERR_INVALID_ARGUMENT (detail in gar_last_error, NO state change)
+ * for a wrong magic or version, n different from the recorded length, a checksum mismatch, a
+ * fingerprint mismatch, a dry-run blob on a real handle or the reverse, and counters, history
+ * lengths, channel ranges or segment offsets that this handle's design could not have produced.
+ * The fingerprint holds the input and output rate, the total channel count and the channels per
+ * stream, the expanded quality spec (the engine quality for the engine constructors), New path or
+ * engine path, the compute type (GAR_F32 and GAR_F32_EXACT differ) and the number of stages; the
+ * device ordinal is deliberately absent -- restoring on a handle of another GPU is the migration
+ * case.  A handle refusing work after a device error answers GAR_ERR_DEVICE: gar_reset first.
+ * Dry-run handles take part; their blobs hold counters and no rows. */
+int64_t gar_state_size(const gar_resampler *r);
+gar_status gar_state_save(gar_resampler *r, void *buf, int64_t cap, int64_t *n_written);
+gar_status gar_state_load(gar_resampler *r, const void *buf, int64_t n);
+
 /* ---- state / introspection ----------------------------------------------- */
 void gar_reset(gar_resampler *r);                       /* Reset (constant.go:429-444, resampler.go:325-340) */
 double gar_get_ratio(const gar_resampler *r);           /* GetRatio (constant.go:447) */

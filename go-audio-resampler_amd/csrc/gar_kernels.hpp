@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "gar_cubic_seg.hpp"
+
 namespace gar {
 
 // A channel group's input stream seen by a kernel: the retained history
@@ -139,7 +141,7 @@ constexpr int kHxtErrLoadWait = 1, kHxtErrSlotWait = 2;
 
 // A launch whose configuration the device cannot run (dynamic LDS above the kernel's limit): the
 // launcher records what was exceeded here and returns hipErrorInvalidConfiguration; the C-ABI turns
-// it into GAR_ERR_INVALID_ARGUMENT with this message (gar_engine.cpp wrap).
+// it into GAR_ERR_INVALID_ARGUMENT with this message (gar_engine.hpp wrap).
 std::string& launchLimitMsg();
 hipError_t ldsTooBig(const char* kernel, size_t need, size_t limit);
 
@@ -203,16 +205,6 @@ struct PolyDev {
     const void *a, *b, *c, *d;  // [L][T] reversed, compute dtype
     const void* abcd;           // [L][T][4] the same four banks interleaved (poly_kernel's one-load tap)
 };
-
-// CubicStage checkpoint (cubic.go:42-61): before input i (absolute stage-input
-// index) the phase is `phase` and the next output index is o.  Checkpoints are
-// kCubicSegInputs inputs apart.
-struct CubicSeg {
-    double phase;
-    int64_t o, i;
-};
-constexpr int64_t kCubicSegInputs = 256;
-constexpr int kCubicSegInputsShort = 16;  // segment of short calls (closed-form walks only)
 
 // Launchers (all asynchronous on `stream`).  Return hipSuccess or the launch error.
 // Optional history keep folded into a streaming FIR launch: dst[(t - t0) * C + c] = src(t, c) for

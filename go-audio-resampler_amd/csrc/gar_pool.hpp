@@ -1,4 +1,4 @@
-// gar_pool.hpp -- the host worker pool of the large host C-ABI calls (gar_engine.cpp forSlices).
+// gar_pool.hpp -- the host worker pool of the large host C-ABI calls (gar_abi.cpp forSlices).
 // Header-only so the TSan stress test (tools/pool_tsan.cpp) builds it without the HIP runtime.
 #pragma once
 #include <immintrin.h>

@@ -14,7 +14,7 @@
 #include <type_traits>
 
 #include "gar_engine.hpp"
-#include "gar_hxs_launch.hpp"
+#include "gar_hx_launch.hpp"
 #include "gar_pool.hpp"
 
 namespace gar {
@@ -427,7 +427,7 @@ bool isHalf(int32_t t) { return t == GAR_F16 || t == GAR_BF16; }
 bool isNarrow(int32_t t) { return isPcm(t) || isHalf(t); }
 bool ioTypeOk(int32_t t) { return t == GAR_F64 || t == GAR_F32 || t == GAR_F32_EXACT || isNarrow(t); }
 // PCM / half conversion fused into hxs_kernel's loads and stores: one fused split-f16 stage streaming
-// through the row-block kernel (launchHxs's geometry); anything else stages the conversion.
+// through the row-block kernel (hxsPlanFits); anything else stages the conversion.
 bool pcmFusable(const Handle* h) {
     if (h->dry || h->f64 || !h->hx || h->stages.size() != 1 || h->groups.size() != 1) return false;
     const StageRT& st = *h->stages[0];
@@ -845,6 +845,29 @@ gar_status gar_dev_pcm24_convert(const double* in, int64_t n, uint8_t* packed, i
     return GAR_OK;
 }
 
+namespace {
+// The call description of the launch-plan entry points as the launchers' descriptors (addresses as integers).
+void planDescs(int32_t in_type, int64_t in_fs, int64_t in_cs, uint64_t in_addr, int64_t in_base, int64_t in_len,
+               int64_t valid_end, uint64_t hist_addr, int64_t hist_len, int64_t hist_ld, int32_t out_type, uint64_t out_addr,
+               int64_t o0, int64_t out_fs, int64_t out_cs, int64_t o_lo, int64_t o_hi, SrcDesc& src, OutDesc& od) {
+    src = SrcDesc{};
+    src.hist = reinterpret_cast<const void*>(static_cast<uintptr_t>(hist_addr));
+    src.hist_len = hist_len;
+    src.hist_ld = hist_ld;
+    src.in = reinterpret_cast<const void*>(static_cast<uintptr_t>(in_addr));
+    src.in_base = in_base; src.in_len = in_len; src.in_fs = in_fs; src.in_cs = in_cs;
+    src.in_f64 = in_type == GAR_F64;
+    src.in_pcm = isNarrow(in_type) ? in_type : 0;
+    src.valid_end = valid_end;
+    od = OutDesc{};
+    od.out = reinterpret_cast<void*>(static_cast<uintptr_t>(out_addr));
+    od.o0 = o0; od.fs = out_fs; od.cs = out_cs;
+    od.f64 = out_type == GAR_F64;
+    od.pcm = isNarrow(out_type) ? out_type : 0;
+    od.o_lo = o_lo; od.o_hi = o_hi;
+}
+}  // namespace
+
 gar_status gar_dev_hxs_plan(const gar_resampler* r, int32_t stage, int32_t in_type, int64_t in_fs, int64_t in_cs,
                             uint64_t in_addr, int64_t in_base, int64_t in_len, int64_t valid_end, uint64_t hist_addr,
                             int64_t hist_len, int64_t hist_ld, int32_t out_type, uint64_t out_addr, int64_t o0,
@@ -856,26 +879,38 @@ gar_status gar_dev_hxs_plan(const gar_resampler* r, int32_t stage, int32_t in_ty
     const gar::StageRT& st = *r->stages[stage];
     const HxDev* hx = st.fusedD.hx ? st.fusedD.hx : (st.dftD.hx ? st.dftD.hx : st.decimD.hx);
     if (!hx) return guard(GAR_ERR_INVALID_ARGUMENT, "the stage has no split-f16 plan");
-    SrcDesc src{};
-    src.hist = reinterpret_cast<const void*>(static_cast<uintptr_t>(hist_addr));
-    src.hist_len = hist_len;
-    src.hist_ld = hist_ld;
-    src.in = reinterpret_cast<const void*>(static_cast<uintptr_t>(in_addr));
-    src.in_base = in_base; src.in_len = in_len; src.in_fs = in_fs; src.in_cs = in_cs;
-    src.in_f64 = in_type == GAR_F64;
-    src.in_pcm = isNarrow(in_type) ? in_type : 0;
-    src.valid_end = valid_end;
-    OutDesc od{};
-    od.out = reinterpret_cast<void*>(static_cast<uintptr_t>(out_addr));
-    od.o0 = o0; od.fs = out_fs; od.cs = out_cs;
-    od.f64 = out_type == GAR_F64;
-    od.pcm = isNarrow(out_type) ? out_type : 0;
-    od.o_lo = o_lo; od.o_hi = o_hi;
+    SrcDesc src;
+    OutDesc od;
+    planDescs(in_type, in_fs, in_cs, in_addr, in_base, in_len, valid_end, hist_addr, hist_len, hist_ld, out_type, out_addr, o0,
+              out_fs, out_cs, o_lo, o_hi, src, od);
     buf[0] = 0;
-    if (o_hi <= o_lo) return GAR_OK;  // launchHxs: nothing to launch
+    if (o_hi <= o_lo) return GAR_OK;  // nothing to launch
     const gar::HxsLaunchPlan pl = gar::hxsPlanLaunch(*hx, src, od, channels, cu_count, gar::hxsReadKnobs(), hist_keep > 0, hist_keep);
     if (!pl.ok) std::snprintf(buf, static_cast<size_t>(cap), "not supported\n");
     else gar::hxsTraceLines(pl, od, channels, buf, static_cast<size_t>(cap));
+    return GAR_OK;
+}
+
+gar_status gar_dev_fir_plan(const gar_resampler* r, int32_t stage, int32_t which, int32_t in_type, int64_t in_fs, int64_t in_cs,
+                            uint64_t in_addr, int64_t in_base, int64_t in_len, int64_t valid_end, uint64_t hist_addr,
+                            int64_t hist_len, int64_t hist_ld, int32_t out_type, uint64_t out_addr, int64_t o0,
+                            int64_t out_fs, int64_t out_cs, int64_t o_lo, int64_t o_hi, int32_t channels,
+                            int32_t cu_count, int64_t hist_keep, char* buf, int64_t cap) {
+    if (!r || !buf || cap < 1 || stage < 0 || stage >= static_cast<int32_t>(r->stages.size()) || channels < 1 ||
+        cu_count < 1 || which < 0 || which > 2 || !ioTypeOk(in_type) || !ioTypeOk(out_type))
+        return guard(GAR_ERR_INVALID_ARGUMENT, "bad launch-plan arguments");
+    const gar::StageRT& st = *r->stages[stage];
+    BgDev p = which == 0 ? st.fusedD : (which == 1 ? st.dftD : st.decimD);
+    if (p.Pc <= 0) return guard(GAR_ERR_INVALID_ARGUMENT, "the stage has no such FIR plan");
+    // a dry-run handle uploads no tables: its row-block-aligned plans get the non-null table pointer they
+    // have on a device (the planner tests it, nothing dereferences it)
+    if (p.rbAligned && !p.rbStart) p.rbStart = p.hRbStart;
+    SrcDesc src;
+    OutDesc od;
+    planDescs(in_type, in_fs, in_cs, in_addr, in_base, in_len, valid_end, hist_addr, hist_len, hist_ld, out_type, out_addr, o0,
+              out_fs, out_cs, o_lo, o_hi, src, od);
+    const gar::FirLaunchPlan pl = gar::firPlanLaunch(p, src, od, channels, cu_count, gar::firReadKnobs(), hist_keep > 0, hist_keep);
+    gar::firTraceLines(pl, p, src, od, channels, buf, static_cast<size_t>(cap));
     return GAR_OK;
 }
 

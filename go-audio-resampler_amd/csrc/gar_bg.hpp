@@ -5,6 +5,7 @@
 
 #include <algorithm>
 
+#include "gar_bg_geo.hpp"
 #include "gar_kernels.hpp"
 #include "gar_plan.hpp"
 
@@ -120,26 +121,6 @@ __device__ GAR_BG_NF_ATTR void bgNfFixRange(BgArgsP ka, int64_t a0, int na, int 
 #define GAR_BG_DEV 0
 #endif
 constexpr bool kBgDev = GAR_BG_DEV;
-constexpr size_t kBgStaticLds = 64;  // bg_kernel's static LDS (nfFlag), rounded up
-constexpr int kBgProfWords = 64;
-
-struct BgGrid {
-    int Pc, Qc, Kc, W, Wl, Ws, G;
-    int64_t a_lo;
-    int nchunk, ncols, nblocks;
-    int C, nprog, kch, nwt, ncg, nred, nslots, parity;
-    int dbg;  // development timing knob (GAR_BG_DBG): 1 skip tile DMA after the first, 2 skip stores
-    int vst;  // f32 epilogue: 0 scalar, 1 channel-contiguous (fs == 1), 2 stereo interleaved (C == 2, fs == 2, cs == 1)
-    int rbMode;  // small launch of a row-block-aligned plan: bg_rb_kernel (G = 1)
-    // bg_rb_kernel: program ranges and first input rows passed by value (kernarg), so a wave issues
-    // its A and B loads without first loading its program from the tables
-    int rbStart[kBgRbKMaxRb + 1];
-    int rbK0[kBgRbKMaxProg];
-    void* hdst;       // folded history keep (HistCopy): hdst[(t - ht0) * C + c] = src(t, c), t < ht0 + hn
-    int64_t ht0, hn;
-    unsigned long long* prof;  // development stamps (kBgDev), else null
-};
-
 // Development: phase stamps of waves 0 and 1 of a workgroup's first item (words base + 8 wt + k:
 // k = 0..5 phase cycles, 6 count) and the workgroup's life (base + 16: count, life sum, first entry,
 // last exit, last entry; s_memrealtime ticks of 10 ns).
@@ -945,13 +926,7 @@ __device__ __forceinline__ void bgRbItem(const BgDev& p, const SrcDesc& src, con
     stm.done(g, 32);
 }
 
-// XCD-grouped item order of the small launches: workgroup slot bb runs item (group, member) with
-// group = 8 (bb / 8 / M) + bb % 8 and member = (bb / 8) % M, so the M items that read the same
-// input lines (the row blocks of one column block; the row blocks x channels of one time block) run
-// on workgroup slots of one residue mod 8, i.e. on one XCD under the round-robin dispatch, and share
-// its L2 (cfg5 decimator: each 64-B line of the 8-channel stream was fetched by 8 XCDs).  The grid
-// is 8 M ceil(ngroups / 8) slots (a multiple of 8 also when capped); slots past the last group idle.
-__host__ __device__ inline int64_t bgXcdSlots(int64_t ngroups, int64_t M) { return 8 * M * ((ngroups + 7) / 8); }
+// Item (group, member) of workgroup slot bb in the XCD-grouped order of the small launches (bgXcdSlots).
 __device__ __forceinline__ bool bgXcdItem(int64_t bb, int M, int ngroups, int& group, int& member) {
     const int64_t rest = bb >> 3;
     member = static_cast<int>(rest % M);
@@ -987,15 +962,8 @@ __global__ __launch_bounds__(64 * kBgRbMaxWaves) void bg_rb_kernel(BgArgs ka) {
 // Kread rows of channel c) is staged once in LDS by all waves (one memory round trip of ~4 loads
 // per thread instead of every wave gathering NS rows of 16 columns), then wave w runs program
 // rbStart[rb] + w with B read from LDS.  LDS rows are padded by kRtPad(Qc) every Qc rows so the 16
-// columns of a B read (Qc rows apart) fall on distinct bank pairs.  Same A, same B values, same
-// MFMA order and program-order reduction as bg_kernel / bg_rb_kernel: the same bits.
-__host__ __device__ constexpr int kRtPad(int Qc) { return ((2 - Qc) % 32 + 32) % 32; }  // (Qc + pad) % 32 == 2
-inline size_t bgRtLds(int Qc, int Kread, int nprog, size_t esz) {
-    const int nrow = 15 * Qc + Kread;
-    const size_t win = (static_cast<size_t>(nrow) + static_cast<size_t>(kRtPad(Qc)) * (nrow / Qc + 1)) * esz;
-    return (win + 15) / 16 * 16 + static_cast<size_t>(nprog) * 64 * 4 * esz;
-}
-
+// columns of a B read (Qc rows apart) fall on distinct bank pairs (gar_bg_geo.hpp).  Same A, same B
+// values, same MFMA order and program-order reduction as bg_kernel / bg_rb_kernel: the same bits.
 // Redo of a bg_rt_kernel item whose outputs hold a non-finite value (all waves; the window is still
 // in LDS): its non-finite samples set to 0 and their rows recorded (nf[0] lo, nf[1] hi), the programs
 // rerun from the clean window, the sums stored, then the outputs whose real window holds a non-finite

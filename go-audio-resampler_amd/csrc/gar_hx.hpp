@@ -138,7 +138,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t hxRsrc(const float* base) {
 
 // Global loads of interior block bl's items into registers (issued, not waited
 // on).  Formats 0-2: one buffer resource per block (its first chunk, 64-bit
-// base) and per-slot 32-bit scalar offsets (launchHx checks they fit);
+// base) and per-slot 32-bit scalar offsets (hxPlanLaunch checks they fit);
 // format 3: 64-bit per-lane addresses (strides too large for that).
 __device__ __forceinline__ void hxLoad(const HxArgs& x, const HxItems& it, int bl, int lane, f32x4 (&v)[kHxJ]) {
     const uint32_t fsB = static_cast<uint32_t>(x.in_fs) * 4u;
@@ -752,7 +752,7 @@ hipError_t hxLaunch(const HxArgs& x, int waves, size_t lds, int64_t blocks, int6
     return hipGetLastError();
 }
 
-// every instantiation launchHx can reach: RB NS 1..10 x store layouts 0..3, SEG NS 2..8 (even)
+// every instantiation launchHxPlan can reach: RB NS 1..10 x store layouts 0..3, SEG NS 2..8 (even)
 #define GAR_HX_FOR_RB(M, NS) M(NS, true, 0) M(NS, true, 1) M(NS, true, 2) M(NS, true, 3)
 #define GAR_HX_FOR_ALL(M)                                                                              \
     GAR_HX_FOR_RB(M, 1) GAR_HX_FOR_RB(M, 2) GAR_HX_FOR_RB(M, 3) GAR_HX_FOR_RB(M, 4) GAR_HX_FOR_RB(M, 5) \

@@ -8,13 +8,13 @@
 #include <utility>
 #include <vector>
 
-#include "gar_hxs_launch.hpp"
+#include "gar_hx_launch.hpp"
 #include "gar_hxt.hpp"
 
 namespace gar {
 
 // instantiations live in gar_hxs_i1.hip / gar_hxs_i2.hip / gar_hxs_i3.hip (compiled in parallel)
-#define GAR_HXS_EXT(NS, V) extern template hipError_t hxsLaunch<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t);
+#define GAR_HXS_EXT(NS, V) extern template hipError_t hxsLaunch<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t, int);
 GAR_HXS_FOR_ALL(GAR_HXS_EXT)
 #undef GAR_HXS_EXT
 // hxt_kernel instantiations: gar_hxt_i1.hip / gar_hxt_i2.hip
@@ -110,14 +110,14 @@ hipError_t hxtFmt(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, 
 }
 
 template <int NS>
-hipError_t hxsVst(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st) {
+hipError_t hxsVst(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, int qWaves) {
     switch (x.vst) {
-        case kVstAny: return hxsLaunch<NS, kVstAny>(x, lds, blocks, st);
-        case kVstRows: return hxsLaunch<NS, kVstRows>(x, lds, blocks, st);
-        case kVstStereo: return hxsLaunch<NS, kVstStereo>(x, lds, blocks, st);
-        case kVstStereoPcm16: return hxsLaunch<NS, kVstStereoPcm16>(x, lds, blocks, st);
-        case kVstStereoHalf: return hxsLaunch<NS, kVstStereoHalf>(x, lds, blocks, st);
-        default: return hxsLaunch<NS, kVstF64>(x, lds, blocks, st);
+        case kVstAny: return hxsLaunch<NS, kVstAny>(x, lds, blocks, st, qWaves);
+        case kVstRows: return hxsLaunch<NS, kVstRows>(x, lds, blocks, st, qWaves);
+        case kVstStereo: return hxsLaunch<NS, kVstStereo>(x, lds, blocks, st, qWaves);
+        case kVstStereoPcm16: return hxsLaunch<NS, kVstStereoPcm16>(x, lds, blocks, st, qWaves);
+        case kVstStereoHalf: return hxsLaunch<NS, kVstStereoHalf>(x, lds, blocks, st, qWaves);
+        default: return hxsLaunch<NS, kVstF64>(x, lds, blocks, st, qWaves);
     }
 }
 
@@ -189,14 +189,8 @@ HxsArgs hxsArgsOf(const HxsLaunchPlan& pl, const HxDev& p, const SrcDesc& src, c
 }
 }  // namespace
 
-// hipErrorNotSupported: the plan does not fit this kernel's geometry (the caller uses hx_kernel).
-hipError_t launchHxs(const HxDev& p, const SrcDesc& src, const OutDesc& od, int C, hipStream_t stream, HistCopy* hc) {
-    if (od.o_hi <= od.o_lo) return hipSuccess;
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    const HxsKnobs k = hxsLaunchKnobs();
-    const HxsLaunchPlan pl = hxsPlanLaunch(p, src, od, C, ncu, k, hc && hc->dst, hc ? hc->n : 0);
-    if (!pl.ok) return hipErrorNotSupported;
+hipError_t launchHxsPlan(const HxsLaunchPlan& pl, const HxsKnobs& k, const HxDev& p, const SrcDesc& src, const OutDesc& od, int C,
+                         hipStream_t stream, HistCopy* hc) {
     if (k.trace) {
         char line[512];
         hxsTraceLines(pl, od, C, line, sizeof(line));
@@ -223,7 +217,7 @@ hipError_t launchHxs(const HxDev& p, const SrcDesc& src, const OutDesc& od, int 
         }
     }
     switch (p.NS) {
-#define GAR_HXS_NS(n) case n: return hxsVst<n>(x, pl.lds, blocks, stream);
+#define GAR_HXS_NS(n) case n: return hxsVst<n>(x, pl.lds, blocks, stream, k.hxqW);
 #if !GAR_HXS_QUICK
         GAR_HXS_NS(1) GAR_HXS_NS(2) GAR_HXS_NS(3) GAR_HXS_NS(4) GAR_HXS_NS(5) GAR_HXS_NS(6) GAR_HXS_NS(7)
         GAR_HXS_NS(8)

@@ -1419,11 +1419,10 @@ __global__ __launch_bounds__(64 * kHxqMaxWaves) void hxq_kernel(HxsArgs x) {
 }
 
 template <int NS, int VST>
-hipError_t hxsLaunch(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st) {
+hipError_t hxsLaunch(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, int qWaves) {
     if (x.small && x.qGroups > 0) {  // hxq_kernel: (block, row-block group) workgroups
         if (const size_t lim_ = setMaxLdsOnce(reinterpret_cast<const void*>(&hxq_kernel<NS, VST>)); lim_ < lds) return ldsTooBig("hxq_kernel", lds, lim_);
-        static const int knobW = std::getenv("GAR_HXQ_W") ? std::atoi(std::getenv("GAR_HXQ_W")) : 4;  // waves per workgroup (>= qRbs)
-        const int nw = std::min(kHxqMaxWaves, std::max(std::max(knobW, 1), x.qRbs));
+        const int nw = std::min(kHxqMaxWaves, std::max(std::max(qWaves, 1), x.qRbs));  // waves per workgroup (HxsKnobs::hxqW)
         hipLaunchKernelGGL((hxq_kernel<NS, VST>), dim3(static_cast<unsigned>(blocks * x.qGroups)), dim3(64 * nw), lds, st, x);
         return hipGetLastError();
     }
@@ -1452,6 +1451,6 @@ hipError_t hxsLaunch(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t s
 #define GAR_HXS_FOR_HALF(M) M(1, 5) M(2, 5) M(3, 5) M(4, 5) M(5, 5) M(6, 5) M(7, 5) M(8, 5) M(9, 5) M(10, 5)
 #endif
 #define GAR_HXS_FOR_ALL(M) GAR_HXS_FOR_LO(M) GAR_HXS_FOR_HI(M) GAR_HXS_FOR_HALF(M)
-#define GAR_HXS_INST(NS, V) template hipError_t hxsLaunch<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t);
+#define GAR_HXS_INST(NS, V) template hipError_t hxsLaunch<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t, int);
 
 }  // namespace gar

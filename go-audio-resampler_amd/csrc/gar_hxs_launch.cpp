@@ -5,24 +5,19 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
+
+#include "gar_knobs.hpp"
 
 namespace gar {
 
 // ---- knobs ----------------------------------------------------------------------------------------
 namespace {
-enum KnobKind { kInt, kIsSet, kIsOne };  // atoi of the value; set at all; first character '1'
-struct KnobRow {
-    const char* name;
-    int HxsKnobs::*field;
-    KnobKind kind;
-    bool perLaunch;
-};
 // name, field (its default: the member initialiser in HxsKnobs), how the value reads, when it is read
-constexpr KnobRow kHxsKnobTable[] = {
+constexpr KnobRow<HxsKnobs> kHxsKnobTable[] = {
     {"GAR_HXS_G", &HxsKnobs::g, kInt, false},
     {"GAR_HXS_WGPERCU", &HxsKnobs::wgPerCu, kInt, false},
     {"GAR_HX_TRACE", &HxsKnobs::trace, kIsSet, false},
+    // attribution bits: 1 no loads, 2 no stores, 4 no MFMA, 16 no conversion, 64 consume without converting, 128 no load issue
     {"GAR_HXS_DBG", &HxsKnobs::dbg, kInt, false},
     {"GAR_HXS_PROF", &HxsKnobs::prof, kIsSet, false},
     {"GAR_HXS_SMALL", &HxsKnobs::small, kInt, false},
@@ -36,33 +31,24 @@ constexpr KnobRow kHxsKnobTable[] = {
     {"GAR_HXQ", &HxsKnobs::hxq, kInt, false},
     {"GAR_HXQ_NR", &HxsKnobs::hxqNr, kInt, false},
     {"GAR_HXQ_OPT", &HxsKnobs::hxqOpt, kInt, false},
+    {"GAR_HXQ_W", &HxsKnobs::hxqW, kInt, false},
     {"GAR_HXT_ROLES", &HxsKnobs::roles, kInt, true},
     {"GAR_HXT_WIDE", &HxsKnobs::wide, kInt, true},
     {"GAR_HXT_LEAN", &HxsKnobs::lean, kInt, true},
     {"GAR_HXT_FAULT", &HxsKnobs::fault, kIsOne, true},
 };
-
-void readKnobs(HxsKnobs& k, bool perLaunchOnly) {
-    for (const KnobRow& r : kHxsKnobTable) {
-        if (perLaunchOnly && !r.perLaunch) continue;
-        const char* e = std::getenv(r.name);
-        if (r.kind == kIsSet) k.*r.field = e != nullptr;
-        else if (r.kind == kIsOne) k.*r.field = e && e[0] == '1';
-        else k.*r.field = e ? std::atoi(e) : HxsKnobs{}.*r.field;
-    }
-}
 }  // namespace
 
 HxsKnobs hxsReadKnobs() {
     HxsKnobs k;
-    readKnobs(k, false);
+    readKnobTable(kHxsKnobTable, k, false);
     return k;
 }
 
 HxsKnobs hxsLaunchKnobs() {
     static const HxsKnobs perProcess = hxsReadKnobs();
     HxsKnobs k = perProcess;
-    readKnobs(k, true);
+    readKnobTable(kHxsKnobTable, k, true);
     return k;
 }
 

@@ -3,7 +3,7 @@
 // load / store layout, chunking, group size and ring, compute-wave roles, block order -- from integers
 // alone (plan fields, strides, address alignments, the CU count, the knobs): no HIP call, no pointer
 // dereferenced, so it runs and is tested on a machine without a GPU (gar.h gar_dev_hxs_plan).
-// launchHxs (gar_hxs.hip) fills HxsArgs from the result and dispatches.
+// launchHxsPlan (gar_hxs.hip) fills HxsArgs from the result and dispatches.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -33,6 +33,7 @@ struct HxsKnobs {
     int hxq = 1;          // GAR_HXQ: 0 keeps hxs_small_kernel where hxq_kernel applies
     int hxqNr = 0;        // GAR_HXQ_NR: row blocks per hxq workgroup (0: by the CU count)
     int hxqOpt = 1;       // GAR_HXQ_OPT: hxq_kernel variant (HxsArgs::qOpt)
+    int hxqW = 4;         // GAR_HXQ_W: waves per hxq workgroup (hxsLaunch clamps it to [max(1, qRbs), kHxqMaxWaves])
     // re-read on every launch (tests switch them inside one process)
     int roles = -1;       // GAR_HXT_ROLES: 1 balanced compute roles, 0 one wave per row block, unset: by plan
     int wide = 1;         // GAR_HXT_WIDE: 0 keeps 16-channel blocks where 32-channel blocks apply

@@ -325,7 +325,7 @@ __device__ __forceinline__ void hxtConvert(const HxsArgs& x, const HxsStage& st,
 // means every earlier item is complete, and a waiter checks only the last item it needs: group g
 // runs once load P+g-1 is complete (its window: loads 0 .. P+g-1); load j may overwrite ring rows
 // once the last group whose window held them is complete (hxtFreeNeed).  A producer runs at most
-// (ring slots + 2) items ahead of the slowest one (host check in launchHxs), fewer than kHxtSlots,
+// (ring slots + 2) items ahead of the slowest one (host check in hxsPlanLaunch), fewer than kHxtSlots,
 // so a slot never holds arrivals of two laps at once and a count never runs past n * (lap + 1).
 // A producer arrives after s_waitcnt lgkmcnt(0) (its ring writes / reads done), and LDS executes
 // one wave's operations in order, so a waiter that sees the count and then reads the ring sees the

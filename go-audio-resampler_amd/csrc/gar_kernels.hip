@@ -25,6 +25,7 @@
 #include <map>
 
 #include "gar_bg.hpp"
+#include "gar_hx_launch.hpp"
 #include "gar_kernels.hpp"
 
 namespace gar {
@@ -67,17 +68,14 @@ hipError_t bgLaunchF32a(int NS, const BgDev& p, const SrcDesc& src, const OutDes
 hipError_t bgLaunchF32b(int NS, const BgDev& p, const SrcDesc& src, const OutDesc& od, const BgGrid& g, int threads,
                         size_t lds, int64_t blocks, hipStream_t st, bool globalB);
 
-// Small-launch geometry of a row-block-aligned f64 plan (stream chunks): returns the launch mode
-// (0 not a small launch; 1 bg_rb_kernel, 2 bg_rt_kernel) with g, the dynamic LDS and
-// the grid filled in.  The history keep hc is taken (hc->done) when the mode is not 0.
 // development: GAR_BG_PROF=1 (with a -DGAR_BG_DEV=1 build of the f64 units) sums the small
 // launches' phase stamps and prints them at exit
-static unsigned long long* bgProfBuf() {
+static unsigned long long* bgProfBuf(bool on) {
     static unsigned long long* p = nullptr;
     static bool init = false;
     if (!init) {
         init = true;
-        if (std::getenv("GAR_BG_PROF") && hipMalloc(&p, kBgProfWords * sizeof(unsigned long long)) == hipSuccess) {
+        if (on && hipMalloc(&p, kBgProfWords * sizeof(unsigned long long)) == hipSuccess) {
             (void)hipMemset(p, 0, kBgProfWords * sizeof(unsigned long long));
             (void)hipMemset(p + 18, 0xff, sizeof(unsigned long long));
             (void)hipMemset(p + 32 + 18, 0xff, sizeof(unsigned long long));
@@ -101,162 +99,51 @@ static unsigned long long* bgProfBuf() {
     return p;
 }
 
-static int bgSmallGrid(const BgDev& p, const OutDesc& od, int C, HistCopy* hc, int ncu, BgGrid& g, size_t& lds,
-                       int64_t& blocks) {
-    static const int knobDbg = std::getenv("GAR_BG_DBG") ? std::atoi(std::getenv("GAR_BG_DBG")) : 0;
-    const int64_t a_lo = od.o_lo / p.Pc;
-    const int64_t a_hi = (od.o_hi + p.Pc - 1) / p.Pc;
-    const int64_t nmac = a_hi - a_lo;
-    // small launch of a row-block-aligned f64 plan (stream chunks): one (column block, row block) per
-    // workgroup, one macro period per column (bg_rb_kernel) -- same programs, same sums
-    if (!(p.f64 && p.rbAligned && p.rbStart && p.hRbStart && p.nrb <= kBgRbKMaxRb && p.nprog <= kBgRbKMaxProg &&
-          (nmac * C + 15) / 16 <= 2 * static_cast<int64_t>(ncu) && !(knobDbg & 8)))
-        return 0;
-    g.Pc = p.Pc; g.Qc = p.Qc; g.Kc = p.Kc; g.C = C;
-    g.nprog = p.nprog;
-    g.kch = p.kch;
-    g.nwt = p.nw;
-    g.ncg = p.ncg;
-    g.nred = p.nred;
-    g.nslots = p.nslots;
-    g.a_lo = a_lo;
-    g.rbMode = 1;
-    for (int i = 0; i <= p.nrb; ++i) g.rbStart[i] = p.hRbStart[i];
-    for (int i = 0; i < p.nprog; ++i) g.rbK0[i] = p.hRbK0[i];
-    g.G = 1;
-    g.W = p.Kc;
-    g.Wl = p.Kread;
-    g.Ws = g.Wl;
-    g.nchunk = static_cast<int>(nmac);
-    g.ncols = static_cast<int>(nmac * C);
-    g.nblocks = (g.ncols + 15) / 16;
-    g.dbg = knobDbg;
-    g.vst = 0;
-    g.parity = 0;
-    g.hdst = nullptr;
-    g.ht0 = g.hn = 0;
-    g.prof = kBgDev ? bgProfBuf() : nullptr;
-    if (hc && hc->n > 0 && hc->dst) {
-        g.hdst = hc->dst;
-        g.ht0 = hc->t0;
-        g.hn = hc->n;
-        hc->done = true;
-    }
-    // time-major (bg_rt_kernel, knob GAR_BG_RT=0: bg_rb_kernel): workgroups = row blocks x channels
-    // x blocks of 16 consecutive macro periods, each window staged once in LDS
-    // Default: time-major for plans of one or two row blocks (the integer decimator: each window is
-    // staged once; 4800-frame cfg5 calls 26.8 -> 18.9 us), bg_rb_kernel otherwise (a plan of ten row
-    // blocks would stage every window ten times: the cfg5 composite 21.8 -> 33.6 us).
-    static const int knobRt = std::getenv("GAR_BG_RT") ? std::atoi(std::getenv("GAR_BG_RT")) : -1;
-    const size_t rtLds = bgRtLds(p.Qc, p.Kread, p.maxPrb, 8);
-    if ((knobRt == 1 || (knobRt < 0 && p.nrb <= 2)) && rtLds <= 64 * 1024) {
-        g.rbMode = 2;
-        const int64_t nkb = (nmac + 15) / 16;
-        blocks = std::min<int64_t>(bgXcdSlots(nkb, static_cast<int64_t>(C) * p.nrb), 65528);  // XCD-grouped slots
-        lds = rtLds;
-        return 2;
-    }
-    blocks = std::min<int64_t>(bgXcdSlots(g.nblocks, p.nrb), 65528);  // XCD-grouped slots
-    lds = 0;
-    return 1;
-}
-
-static int numCUs() {
+int deviceCUs() {
     int dev = 0, ncu = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     return ncu;
 }
 
+// Every x == 0 FIR launch: the CU count, the knobs, the plan (firPlanLaunch: which kernel family and its
+// geometry), then that family's dispatch, which traces from the plan, fills the arguments and launches.
 hipError_t launchBg(const BgDev& p, const SrcDesc& src, const OutDesc& od, int C, hipStream_t stream, HistCopy* hc) {
     if (od.o_hi <= od.o_lo) return hipSuccess;
-    // f32 compute on the split-f16 kernel (every output of the launch, any input dtype)
-    if (p.hx && !p.f64) return launchHx(*p.hx, src, od, C, stream, hc);
-    const int sz = p.f64 ? 8 : 4;
-    BgGrid g;
-    const int ncu = numCUs();
-    {
-        size_t lds = 0;
-        int64_t blocks = 0;
-        if (bgSmallGrid(p, od, C, hc, ncu, g, lds, blocks))
-            return bgLaunchF64(p.NS, p, src, od, g, 64 * p.maxPrb, lds, blocks, stream, false);
+    const int ncu = deviceCUs();
+    const FirKnobs k = firLaunchKnobs();
+    const FirLaunchPlan pl = firPlanLaunch(p, src, od, C, ncu, k, hc && hc->dst, hc ? hc->n : 0);
+    switch (pl.path) {
+        case FirPath::Bg: return launchBgPlan(pl.bg, k.bg, p, src, od, stream, hc);
+        case FirPath::Hxs: return launchHxsPlan(pl.hxs, k.hxs, *p.hx, src, od, C, stream, hc);
+        case FirPath::Hx: return launchHxPlan(pl.hx, k.hx, *p.hx, src, od, C, stream);
+        default: return hipSuccess;
     }
-    g.Pc = p.Pc; g.Qc = p.Qc; g.Kc = p.Kc; g.C = C;
-    // Tuning knobs (development sweeps only; defaults are the tuned values).
-    static const int knobG = std::getenv("GAR_BG_G") ? std::atoi(std::getenv("GAR_BG_G")) : 0;
-    static const int knobWgPerCu = std::getenv("GAR_BG_WGPERCU") ? std::atoi(std::getenv("GAR_BG_WGPERCU")) : 0;
-    static const int knobDbg = std::getenv("GAR_BG_DBG") ? std::atoi(std::getenv("GAR_BG_DBG")) : 0;
-    static const bool knobNoVst = std::getenv("GAR_BG_NOVST") != nullptr;
-    static const bool knobNoParity = std::getenv("GAR_BG_NOPARITY") != nullptr;
-    g.rbMode = 0;
-    g.nprog = p.nprog;
-    g.kch = p.kch;
-    g.nwt = p.nw;
-    g.ncg = p.ncg;
-    g.nred = p.nred;
-    g.nslots = p.nslots;
-    g.a_lo = od.o_lo / p.Pc;
-    const int64_t a_hi = (od.o_hi + p.Pc - 1) / p.Pc;
-    const int64_t nmac = a_hi - g.a_lo;
-    const int threads = 64 * g.ncg * g.nwt;
-    const int tileN = 16 * g.ncg;
-    const size_t slotBytes = static_cast<size_t>(g.ncg) * g.nslots * 256 * sz;
-    // Two LDS tiles (double buffer) + partial slots (two buffers when they fit
-    // beside a tile of >= 4 macro periods, else one + a second barrier).
-    const int rowsPerPiece = p.f64 ? 2 : 4;
-    auto wsFor = [&](int W) { return (W + rowsPerPiece - 1) / rowsPerPiece * rowsPerPiece; };
-    auto tileBytes = [&](int G) { return 2 * static_cast<size_t>(tileN) * wsFor(p.Kread + (G - 1) * p.Qc) * sz; };
-    const size_t kLds = 160 * 1024 - kBgStaticLds;  // bg_kernel's static LDS: the non-finite ranges
-    g.parity = (g.nred > 0 && !knobNoParity && tileBytes(std::min<int64_t>(4, std::max<int64_t>(nmac, 1))) + 2 * slotBytes <= kLds) ? 1 : 0;
-    const size_t partBytes = (g.parity ? 2 : 1) * slotBytes;
-    int G = 1;
-    for (int cand = 2; cand <= 8; ++cand) {
-        if (cand > nmac) break;
-        if (tileBytes(cand) + partBytes > kLds) break;
-        G = cand;
+}
+
+hipError_t launchBgPlan(const BgLaunchPlan& pl, const BgKnobs& k, const BgDev& p, const SrcDesc& src, const OutDesc& od,
+                        hipStream_t stream, HistCopy* hc) {
+    if (pl.outcome == BgOutcome::Invalid) return hipErrorInvalidConfiguration;
+    if (pl.outcome == BgOutcome::Nothing) return hipSuccess;
+    static int traced = 0;
+    if (k.trace && traced < 64) {
+        ++traced;
+        char line[768];
+        bgTraceLine(pl, p, od, line, sizeof(line));
+        fputs(line, stderr);
     }
-    if (knobG > 0 && knobG < G) G = knobG;
-    g.G = G;
-    g.W = p.Kc + (G - 1) * p.Qc;
-    g.Wl = p.Kread + (G - 1) * p.Qc;
-    g.Ws = wsFor(g.Wl);
-    const int64_t nchunk = (nmac + G - 1) / G;
-    g.nchunk = static_cast<int>(nchunk);
-    g.ncols = static_cast<int>(nchunk * C);
-    g.nblocks = (g.ncols + tileN - 1) / tileN;
-    g.dbg = knobDbg;
-    g.vst = 0;
-    if (!p.f64 && !od.f64 && !od.pcm && !knobNoVst) {
-        if (od.fs == 1) g.vst = 1;
-        else if (C == 2 && od.fs == 2 && od.cs == 1) g.vst = 2;
-    }
-    size_t lds = tileBytes(G) + partBytes;
-    const bool globalB = lds > kLds;
-    if (globalB) lds = partBytes;
-    if (lds > kLds) return hipErrorInvalidConfiguration;
-    if (g.nblocks <= 0) return hipSuccess;
-    int64_t blocks = std::min<int64_t>(g.nblocks, static_cast<int64_t>(ncu) * (knobWgPerCu > 0 ? knobWgPerCu : 2));
-    g.hdst = nullptr;
-    g.prof = nullptr;
-    g.ht0 = g.hn = 0;
-    if (hc && hc->n > 0 && hc->dst) {  // history keep folded into this launch (no gather_kernel after it)
+    BgGrid g = pl.g;
+    if (pl.kernel != BgKernel::Bg && kBgDev) g.prof = bgProfBuf(k.prof != 0);
+    if (pl.histFolded) {  // history keep folded into this launch (no gather_kernel after it)
         g.hdst = hc->dst;
         g.ht0 = hc->t0;
         g.hn = hc->n;
         hc->done = true;
     }
-    static const bool trace = std::getenv("GAR_BG_TRACE") != nullptr;
-    static int traced = 0;
-    if (trace && traced < 64) {
-        ++traced;
-        fprintf(stderr, "bg: f64=%d Pc=%d Qc=%d Kc=%d Kread=%d NS=%d kch=%d nw=%d ncg=%d nprog=%d nred=%d nslots=%d G=%d nmac=%lld C=%d nblocks=%d blocks=%lld lds=%zu globalB=%d o[%lld,%lld)\n",
-                p.f64, p.Pc, p.Qc, p.Kc, p.Kread, p.NS, g.kch, g.nwt, g.ncg, g.nprog, g.nred, g.nslots, g.G,
-                (long long)nmac, C, g.nblocks, (long long)blocks, lds, globalB ? 1 : 0, (long long)od.o_lo, (long long)od.o_hi);
-    }
     hipError_t e;
-    if (p.f64) e = bgLaunchF64(p.NS, p, src, od, g, threads, lds, blocks, stream, globalB);
-    else if (p.NS < 56) e = bgLaunchF32a(p.NS, p, src, od, g, threads, lds, blocks, stream, globalB);
-    else e = bgLaunchF32b(p.NS, p, src, od, g, threads, lds, blocks, stream, globalB);
-    if (e != hipSuccess || !p.nfList) return e;
+    if (pl.unit == BgUnit::F64) e = bgLaunchF64(p.NS, p, src, od, g, pl.threads, pl.lds, pl.blocks, stream, pl.globalB);
+    else if (pl.unit == BgUnit::F32a) e = bgLaunchF32a(p.NS, p, src, od, g, pl.threads, pl.lds, pl.blocks, stream, pl.globalB);
+    else e = bgLaunchF32b(p.NS, p, src, od, g, pl.threads, pl.lds, pl.blocks, stream, pl.globalB);
+    if (pl.kernel != BgKernel::Bg || e != hipSuccess || !p.nfList) return e;
     // the outputs of blocks that staged a non-finite sample (bg_nf_kernel: returns at once when none did)
     const BgArgs ka{p, src, od, g};
     const dim3 ng(static_cast<unsigned>(std::max(1, std::min(g.nblocks, 256)))), nb(256);
@@ -473,8 +360,7 @@ hipError_t launchPoly(const PolyDev& p, const SrcDesc& src, const OutDesc& od, i
     };
     const int CG = alignedFor(4) ? 4 : (alignedFor(2) ? 2 : 1);
     const int64_t total = nout * (C / CG);
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int ncu = deviceCUs();
     // LDS bank: one resident workgroup per CU walks the outputs grid-stride (the bank is copied once
     // per workgroup); without it, enough workgroups to cover the launch.
     const bool lbank = bankB <= kPolyLdsMax && total >= static_cast<int64_t>(ncu) * kPolyThreads;

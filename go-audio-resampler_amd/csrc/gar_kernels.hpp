@@ -209,23 +209,22 @@ struct PolyDev {
 // Launchers (all asynchronous on `stream`).  Return hipSuccess or the launch error.
 // Optional history keep folded into a streaming FIR launch: dst[(t - t0) * C + c] = src(t, c) for
 // t in [t0, t0 + n) (what launchGather does), written by the launch's workgroups after their
-// blocks; `done` set when the launch took it (hxs_kernel only), else the caller gathers.
+// blocks; `done` set when the launch took it (the launch plan's histFolded), else the caller gathers.
 struct HistCopy {
     void* dst = nullptr;
     int64_t t0 = 0, n = 0;
     bool done = false;
 };
 
+// Every x == 0 FIR stage: plans the launch (gar_hx_launch.hpp firPlanLaunch: the bg kernels, the streaming
+// split-f16 kernels or hx_kernel) and dispatches it.
 hipError_t launchBg(const BgDev& p, const SrcDesc& src, const OutDesc& out, int C, hipStream_t stream,
                     HistCopy* hc = nullptr);
-hipError_t launchHx(const HxDev& p, const SrcDesc& src, const OutDesc& out, int C, hipStream_t stream,
-                    HistCopy* hc = nullptr);
-// True when a row-block plan fits launchHxs's geometry at one period per group (its smallest
-// ring), i.e. launchHxs never returns hipErrorNotSupported for it (gar_hxs.hip).
+// True when a row-block plan fits the streaming kernels' geometry at one period per group (its smallest
+// ring), i.e. their planner never declines it (gar_hxs_launch.cpp).
 bool hxsPlanFits(const HxDev& p);
-// Streaming wave-specialised variant of launchHx for row-block plans (gar_hxs.hip).
-hipError_t launchHxs(const HxDev& p, const SrcDesc& src, const OutDesc& out, int C, hipStream_t stream,
-                     HistCopy* hc = nullptr);
+// Compute units of the current device (256 when it cannot be queried).
+int deviceCUs();
 hipError_t launchPoly(const PolyDev& p, const SrcDesc& src, const OutDesc& out, int64_t nout, int C,
                       hipStream_t stream);
 // CubicStage outputs of nseg checkpointed segments (segs readable by the device:

@@ -91,7 +91,7 @@ EXPORTED = [
     "gar_status_string", "gar_last_error", "gar_design_engine", "gar_design_composite", "gar_profile_enable",
     "gar_profile_read", "gar_stage_state", "gar_num_stages", "gar_stage_geometry", "gar_get_statistics",
     "gar_synchronize", "gar_profile_launch_stats", "gar_profile_kinds", "gar_dev_half_convert",
-    "gar_dev_pcm24_convert", "gar_dev_hxs_plan", "gar_state_size", "gar_state_save", "gar_state_load",
+    "gar_dev_pcm24_convert", "gar_dev_hxs_plan", "gar_dev_fir_plan", "gar_state_size", "gar_state_save", "gar_state_load",
 ]
 
 _lib = None
@@ -159,6 +159,8 @@ def lib():
         "gar_dev_half_convert": (i32, [i32, vp, i64, vp, vp, vp]),
         "gar_dev_pcm24_convert": (i32, [vp, i64, vp, vp]),
         "gar_dev_hxs_plan": (i32, [vp, i32, i32, i64, i64, C.c_uint64, i64, i64, i64, C.c_uint64, i64, i64, i32, C.c_uint64,
+                                   i64, i64, i64, i64, i64, i32, i32, i64, C.c_char_p, i64]),
+        "gar_dev_fir_plan": (i32, [vp, i32, i32, i32, i64, i64, C.c_uint64, i64, i64, i64, C.c_uint64, i64, i64, i32, C.c_uint64,
                                    i64, i64, i64, i64, i64, i32, i32, i64, C.c_char_p, i64]),
         "gar_state_size": (i64, [vp]),
         "gar_state_save": (i32, [vp, vp, i64, C.POINTER(i64)]),
@@ -535,6 +537,23 @@ def hxs_plan(r, in_type, in_fs, in_cs, in_addr, in_base, in_len, valid_end, hist
     empty output range.  The knobs are read from the environment on every call."""
     buf = C.create_string_buffer(1024)
     _check(lib().gar_dev_hxs_plan(r._h, int(stage), int(in_type), int(in_fs), int(in_cs), int(in_addr), int(in_base),
+                                  int(in_len), int(valid_end), int(hist_addr), int(hist_len), int(hist_ld), int(out_type),
+                                  int(out_addr), int(o0), int(out_fs), int(out_cs), int(o_lo), int(o_hi), int(channels),
+                                  int(cu_count), int(hist_keep), buf, len(buf)))
+    return buf.value.decode()
+
+
+FIR_FUSED, FIR_DFT, FIR_DECIM = 0, 1, 2
+
+
+def fir_plan(r, in_type, in_fs, in_cs, in_addr, in_base, in_len, valid_end, hist_addr, hist_len, hist_ld,
+             out_type, out_addr, o0, out_fs, out_cs, o_lo, o_hi, channels, cu_count, hist_keep=0, stage=0, which=FIR_FUSED):
+    """Host run of the x == 0 FIR launch planner (gar.h gar_dev_fir_plan) for one call of the stage's fused,
+    DFT or decimator plan on the handle r (a dry-run handle of any compute type will do): the "hxs:" / "hxt:" /
+    "hxq:", "hx:" or "bg:" trace line(s) of that launch, "not supported\\n", "invalid configuration\\n", or ""
+    when nothing launches.  The knobs are read from the environment on every call."""
+    buf = C.create_string_buffer(2048)
+    _check(lib().gar_dev_fir_plan(r._h, int(stage), int(which), int(in_type), int(in_fs), int(in_cs), int(in_addr), int(in_base),
                                   int(in_len), int(valid_end), int(hist_addr), int(hist_len), int(hist_ld), int(out_type),
                                   int(out_addr), int(o0), int(out_fs), int(out_cs), int(o_lo), int(o_hi), int(channels),
                                   int(cu_count), int(hist_keep), buf, len(buf)))

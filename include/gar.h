@@ -325,7 +325,7 @@ gar_status gar_dev_half_convert(int32_t half_type, const double *in, int64_t n, 
 gar_status gar_dev_pcm24_convert(const double *in, int64_t n, uint8_t *packed, int32_t *unpacked);
 
 /* The launch plan of the streaming FIR kernels for one call, computed on the host (no GPU; the
- * planner launchHxs runs, csrc/gar_hxs_launch.hpp): writes the GAR_HX_TRACE line(s) such a launch
+ * planner of every streaming launch, csrc/gar_hxs_launch.hpp): writes the GAR_HX_TRACE line(s) such a launch
  * prints -- kernel, group size, chunking, ring, load / store layout, raw-load rows, compute waves,
  * loaders -- into buf (NUL-terminated, at most cap bytes), "not supported\n" when the planner
  * declines, nothing for an empty output range.  `r` may be a dry-run handle; `stage` picks the
@@ -341,6 +341,21 @@ gar_status gar_dev_hxs_plan(const gar_resampler *r, int32_t stage, int32_t in_ty
                             uint64_t in_addr, int64_t in_base, int64_t in_len, int64_t valid_end, uint64_t hist_addr,
                             int64_t hist_len, int64_t hist_ld, int32_t out_type, uint64_t out_addr, int64_t o0,
                             int64_t out_fs, int64_t out_cs, int64_t o_lo, int64_t o_hi, int32_t channels,
+                            int32_t cu_count, int64_t hist_keep, char *buf, int64_t cap);
+
+/* The launch of one x == 0 FIR stage call as the engine would make it, planned on the host (no GPU;
+ * csrc/gar_hx_launch.hpp firPlanLaunch): the call description of gar_dev_hxs_plan plus `which` plan of
+ * the stage -- 0 fused composite, 1 DFT, 2 decimator (GAR_ERR_INVALID_ARGUMENT if the stage has none).
+ * `r` may be a dry-run handle of any compute type.  Writes the line(s) the launch prints under
+ * GAR_HX_TRACE / GAR_BG_TRACE -- the "hxs:" / "hxt:" / "hxq:" lines of the streaming split-f16 kernels,
+ * an "hx:" line (the block kernel) or a "bg:" line (GAR_F64 / GAR_F32_EXACT compute), every field of the
+ * plan -- or "not supported\n" (PCM output on the block kernel), "invalid configuration\n", nothing
+ * when there is nothing to launch.  The knobs are read from the environment on every call.  For tests
+ * (CPU suite). */
+gar_status gar_dev_fir_plan(const gar_resampler *r, int32_t stage, int32_t which, int32_t in_type, int64_t in_fs,
+                            int64_t in_cs, uint64_t in_addr, int64_t in_base, int64_t in_len, int64_t valid_end,
+                            uint64_t hist_addr, int64_t hist_len, int64_t hist_ld, int32_t out_type, uint64_t out_addr,
+                            int64_t o0, int64_t out_fs, int64_t out_cs, int64_t o_lo, int64_t o_hi, int32_t channels,
                             int32_t cu_count, int64_t hist_keep, char *buf, int64_t cap);
 
 /* ---- host-only design introspection (no GPU needed) ----------------------- */

@@ -472,7 +472,17 @@ gar_status deviceCall(Handle* r, const DevIo* in, int64_t frames, const DevIo& o
                 }
             }
         }
-        const bool fuse = fuseAny && out.dtype != GAR_PCM24_PACKED;
+        // a flush that would leave the composite launch (fusedFlushQuirk) ends in kernels that store no PCM
+        const bool fuse = fuseAny && out.dtype != GAR_PCM24_PACKED &&
+                          !(flush && isNarrow(out.dtype) && fusedFlushQuirk(r, r->groups[0]));
+        // dither of an integer PCM output: the position of the call's first frame is the group's samplesOut now
+        Dither dz;
+        if (r->ditherMode != GAR_DITHER_NONE && isPcm(out.dtype)) {
+            dz.mode = r->ditherMode;
+            dz.seedLo = static_cast<uint32_t>(r->ditherSeed);
+            dz.seedHi = static_cast<uint32_t>(r->ditherSeed >> 32);
+            dz.pos0 = r->groups[0].statOut;
+        }
         OutView ov;
         ov.p = out.p;
         ov.f64 = out.dtype == GAR_F64 ? 1 : 0;
@@ -481,7 +491,10 @@ gar_status deviceCall(Handle* r, const DevIo* in, int64_t frames, const DevIo& o
         const bool stageOut = isNarrow(out.dtype) && !fuse && !r->dry;
         if (isNarrow(out.dtype)) {
             ov.f64 = 0;
-            if (fuse) ov.pcm = out.dtype;
+            if (fuse) {
+                ov.pcm = out.dtype;
+                ov.dz = dz;
+            }
         }
         if (stageOut) {
             std::vector<int64_t> sz;
@@ -492,7 +505,7 @@ gar_status deviceCall(Handle* r, const DevIo* in, int64_t frames, const DevIo& o
         gar_status st;
         const int64_t got = runGroup(r, r->groups[0], iv, ov, flush, s, out_cap, st);
         if (st == GAR_OK && stageOut && got > 0)
-            HIPCHK(launchConvert(r->outStage.p, r->cf(), C, 1, out.p, out.dtype, out.fs, out.cs, got, C, s));
+            HIPCHK(launchConvert(r->outStage.p, r->cf(), C, 1, out.p, out.dtype, out.fs, out.cs, got, C, s, dz));
         if (st == GAR_OK && out_frames) *out_frames = got;
         return st;
     });
@@ -829,6 +842,38 @@ gar_status gar_dev_half_convert(int32_t half_type, const double* in, int64_t n, 
         if (from_f64) from_f64[i] = b;
         if (from_f32) from_f32[i] = halfOfF32(static_cast<float>(in[i]), half_type);
         if (widened) widened[i] = halfToF32(b, half_type);
+    }
+    return GAR_OK;
+}
+
+gar_status gar_set_dither(gar_resampler* r, int32_t mode, uint64_t seed) {
+    if (!r) return guard(GAR_ERR_INVALID_ARGUMENT, "nil resampler");
+    if (mode != GAR_DITHER_NONE && mode != GAR_DITHER_TPDF) return guard(GAR_ERR_INVALID_ARGUMENT, "unknown dither mode");
+    static_assert(kDitherNone == GAR_DITHER_NONE && kDitherTpdf == GAR_DITHER_TPDF, "the kernels' dither modes are the ABI's");
+    r->ditherMode = mode;
+    r->ditherSeed = seed;
+    return GAR_OK;
+}
+
+gar_status gar_get_dither(const gar_resampler* r, int32_t* mode, uint64_t* seed, int64_t* position) {
+    if (!r) return guard(GAR_ERR_INVALID_ARGUMENT, "nil resampler");
+    if (mode) *mode = r->ditherMode;
+    if (seed) *seed = r->ditherSeed;
+    if (position) *position = r->groups.size() == 1 ? r->groups[0].statOut : -1;
+    return GAR_OK;
+}
+
+gar_status gar_dev_dither_quantize(int32_t pcm_type, uint64_t seed, int32_t channel, int64_t position0, const double* in,
+                                   int64_t n, int32_t* out, double* noise) {
+    if (!isPcm(pcm_type) || n < 0 || (n > 0 && !in && out) || channel < 0)
+        return guard(GAR_ERR_INVALID_ARGUMENT, "bad dither quantizer arguments");
+    const uint32_t lo = static_cast<uint32_t>(seed), hi = static_cast<uint32_t>(seed >> 32);
+    const uint32_t key = ditherKey(lo, hi, static_cast<uint32_t>(channel));
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t p = static_cast<uint64_t>(position0) + static_cast<uint64_t>(i);
+        if (noise) noise[i] = ditherNoise(ditherKeyHi(key, static_cast<uint32_t>(p >> 32)), static_cast<uint32_t>(p));
+        // what the kernels store (pcmDitherAt: the checked stores and the staged kernels call it as is)
+        if (out) out[i] = pcmDitherAt(in[i], pcm_type, lo, hi, static_cast<uint32_t>(channel), p);
     }
     return GAR_OK;
 }

@@ -94,6 +94,10 @@ OutDesc mkOut(const OutView& o, int64_t o0, int64_t n) {
     d.pcm = o.pcm;
     d.o_lo = o0;
     d.o_hi = o0 + n;
+    d.dither = o.dz.mode;
+    d.dseedLo = o.dz.seedLo;
+    d.dseedHi = o.dz.seedHi;
+    d.dpos0 = o.dz.pos0;
     return d;
 }
 
@@ -270,6 +274,14 @@ int64_t stageProcess(Ctx& x, int si, const InView& in, const OutView& out) {
     }
 }
 
+// The view `rows` frames further on; the dither position travels with the base.
+OutView offsetView(const OutView& o, int64_t rows) {
+    OutView r = o;
+    if (o.p) r.p = static_cast<char*>(o.p) + rows * o.fs * (o.pcm ? pcmBytes(o.pcm) : (o.f64 ? 8 : 4));
+    r.dz.pos0 += rows;
+    return r;
+}
+
 // engine.Resampler.Flush for one stage (resampler.go:275-322).
 int64_t stageFlush(Ctx& x, int si, const OutView& out) {
     StageRT& rt = *x.h->stages[si];
@@ -336,8 +348,7 @@ int64_t stageFlush(Ctx& x, int si, const OutView& out) {
                 uz.zeros = true;
                 uz.n = d.poly.taps;
                 const SrcDesc usrc = mkSrc(dv.uh, C, before.u_count, uz);
-                OutView o2 = out;
-                if (x.launch && nout > 0) o2.p = static_cast<char*>(out.p) + total * out.fs * (out.f64 ? 8 : 4);
+                const OutView o2 = offsetView(out, total);
                 polyLaunch(x, rt, before, usrc, o2, y0, nout);
                 hist_update(x, dv.uh, usrc, c.u_base, c.u_count);
                 c.y_count += nout;
@@ -348,12 +359,6 @@ int64_t stageFlush(Ctx& x, int si, const OutView& out) {
         default:
             return 0;
     }
-}
-
-OutView offsetView(const OutView& o, int64_t rows) {
-    OutView r = o;
-    if (o.p) r.p = static_cast<char*>(o.p) + rows * o.fs * (o.pcm ? pcmBytes(o.pcm) : (o.f64 ? 8 : 4));
-    return r;
 }
 
 // Where stage i of the chain writes: the caller's output for the last stage, else (when launching) the
@@ -494,6 +499,17 @@ int64_t simulate(Handle* h, Group& g, int64_t n, bool flush, std::vector<int64_t
     in.n = n;
     OutView o;
     return flush ? chainFlush(x, o, sizes) : chainProcess(x, in, o, sizes);
+}
+
+bool fusedFlushQuirk(const Handle* h, const Group& g) {
+    if (h->stages.size() != 1 || g.cnt.empty() || g.cnt[0].staged) return false;
+    const EngineDesign& d = h->stages[0]->d;
+    if (d.kind != EngineKind::DftPoly) return false;
+    Counters t = g.cnt[0];  // stageFlush's count of the fused flush
+    bool quirk = false;
+    if (t.dft_hist > 0) cntPoly(t, d.poly, cntDft(t, d.dft, d.dft.taps), quirk);
+    if (t.poly_hist > 0) cntPoly(t, d.poly, d.poly.taps, quirk);
+    return quirk;
 }
 
 int64_t runGroup(Handle* h, Group& g, const InView& in, const OutView& out, bool flush, hipStream_t s,

@@ -116,6 +116,7 @@ struct OutView {
     int64_t fs = 0, cs = 0;
     int f64 = 0;
     int pcm = 0;  // integer PCM output bits, or GAR_F16 / GAR_BF16 (fused into hxs_kernel's stores)
+    Dither dz;    // dither of a fused integer PCM store; dz.pos0 = stream position of the view's first frame
     // interleaved [t][C] rows of the compute type (histories, stage-boundary scratch, staged conversions)
     static OutView rows(void* p, int C, int cf) { return OutView{p, C, 1, cf, 0}; }
 };
@@ -262,6 +263,9 @@ struct gar_resampler {
     gar::DevBuf inStage, outStage;
     // state snapshots (gar_state_save / gar_state_load): what the constructor was asked for (the blob's
     // fingerprint; the engine constructors keep no gar_config), the device row image and segment table
+    // gar_set_dither: configuration (not stream state, not in the state blob); the position is the group's statOut
+    int32_t ditherMode = GAR_DITHER_NONE;
+    uint64_t ditherSeed = 0;
     double fpInRate = 0, fpOutRate = 0;
     int32_t fpQuality = 0;  // engine.Quality of the engine constructors
     gar::DevBuf stateImg, stateTab;
@@ -301,6 +305,9 @@ Group freshGroup(Handle* h, int c0, int C);
 void isolate(Handle* h, int ch);
 // Dry-run a process (or flush) on copies of the group counters.
 int64_t simulate(Handle* h, Group& g, int64_t n, bool flush, std::vector<int64_t>& sizes);
+// True when a flush of the group's fused DFT+polyphase stage would leave the composite launch for the staged
+// kernels (the polyphase history quirk), which store no PCM: such a flush stages its PCM conversion.
+bool fusedFlushQuirk(const Handle* h, const Group& g);
 // Run one group for real: sizes first (so scratch can be sized), then launches.
 int64_t runGroup(Handle* h, Group& g, const InView& in, const OutView& out, bool flush, hipStream_t s, int64_t cap,
                  gar_status& st);

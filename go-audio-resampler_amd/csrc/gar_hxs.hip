@@ -13,10 +13,14 @@
 
 namespace gar {
 
-// instantiations live in gar_hxs_i1.hip / gar_hxs_i2.hip / gar_hxs_i3.hip (compiled in parallel)
+// instantiations live in gar_hxs_i1.hip / gar_hxs_i2.hip / gar_hxs_i3.hip / gar_hxs_i4.hip (compiled in parallel)
 #define GAR_HXS_EXT(NS, V) extern template hipError_t hxsLaunch<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t, int);
 GAR_HXS_FOR_ALL(GAR_HXS_EXT)
 #undef GAR_HXS_EXT
+// the dither instantiations: gar_hxs_i4.hip
+#define GAR_HXS_EXT_DITHER(NS, V) extern template hipError_t hxsLaunchDither<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t, int);
+GAR_HXS_FOR_DITHER(GAR_HXS_EXT_DITHER)
+#undef GAR_HXS_EXT_DITHER
 // hxt_kernel instantiations: gar_hxt_i1.hip / gar_hxt_i2.hip
 #define GAR_HXT_EXT(NS, F, V, L) extern template hipError_t hxtLaunch<NS, F, V, L>(const HxsArgs&, size_t, int64_t, hipStream_t);
 GAR_HXT_FOR_A(GAR_HXT_EXT)
@@ -112,10 +116,13 @@ hipError_t hxtFmt(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, 
 template <int NS>
 hipError_t hxsVst(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, int qWaves) {
     switch (x.vst) {
-        case kVstAny: return hxsLaunch<NS, kVstAny>(x, lds, blocks, st, qWaves);
+        case kVstAny:
+            return x.dither ? hxsLaunchDither<NS, kVstAny>(x, lds, blocks, st, qWaves) : hxsLaunch<NS, kVstAny>(x, lds, blocks, st, qWaves);
         case kVstRows: return hxsLaunch<NS, kVstRows>(x, lds, blocks, st, qWaves);
         case kVstStereo: return hxsLaunch<NS, kVstStereo>(x, lds, blocks, st, qWaves);
-        case kVstStereoPcm16: return hxsLaunch<NS, kVstStereoPcm16>(x, lds, blocks, st, qWaves);
+        case kVstStereoPcm16:
+            return x.dither ? hxsLaunchDither<NS, kVstStereoPcm16>(x, lds, blocks, st, qWaves)
+                            : hxsLaunch<NS, kVstStereoPcm16>(x, lds, blocks, st, qWaves);
         case kVstStereoHalf: return hxsLaunch<NS, kVstStereoHalf>(x, lds, blocks, st, qWaves);
         default: return hxsLaunch<NS, kVstF64>(x, lds, blocks, st, qWaves);
     }
@@ -156,6 +163,10 @@ HxsArgs hxsArgsOf(const HxsLaunchPlan& pl, const HxDev& p, const SrcDesc& src, c
     x.out = reinterpret_cast<char*>(pl.outBase);
     x.out_fs = od.fs * pl.out_esz;
     x.out_cs = od.cs * pl.out_esz;
+    x.dither = pcmIsInt(od.pcm) ? od.dither : 0;
+    x.dseedLo = od.dseedLo;
+    x.dseedHi = od.dseedHi;
+    x.dpos = od.dpos0 - od.o0;
     x.vst = pl.vst;
     x.ncomp = pl.ncomp;
     for (int w = 0; w < kHxtMaxComp; ++w) x.role[w] = pl.role[w];

@@ -97,6 +97,11 @@ struct HxsArgs {
     int qRbs, qGroups;
     int qU0[12], qRbw[12];  // first window row / row block of each row-block program (HxDev::hU0)
     int qOpt;               // hxq_kernel variants (GAR_HXQ_OPT): 1 barrier after the first load batch issues, 2 buffer-load history keep
+    // TPDF dither of the integer PCM stores (OutDesc::dither), read by the DITHER instantiations only (which such a
+    // launch runs: hxsLaunchDither); last, so no other field moves: output o sits at stream position o + dpos
+    int dither;
+    uint32_t dseedLo, dseedHi;
+    int64_t dpos;
 };
 typedef const __attribute__((address_space(4))) HxsArgs* HxsArgsP;
 
@@ -153,8 +158,22 @@ __device__ __forceinline__ double hxsExact(HxsArgsP x, int64_t a, int r, int c) 
     return y;
 }
 
+// outWrite of the fixups; DITHER (the kernels of a launch with dither on, integer PCM output): the sample goes
+// through the dithered quantizer, at the position every other store of the launch gives it.
+template <bool DITHER>
+__device__ __forceinline__ void hxsOutWrite(const OutDesc& od, int64_t o, int c, float v) {
+    if constexpr (DITHER) {
+        if (o < od.o_lo || o >= od.o_hi) return;
+        pcmWriteDither(od.out, (o - od.o0) * od.fs + static_cast<int64_t>(c) * od.cs, od.pcm, static_cast<double>(v), od.dseedLo,
+                       od.dseedHi, static_cast<uint32_t>(c), static_cast<uint64_t>(o - od.o0 + od.dpos0));
+        return;
+    }
+    outWrite<float>(od, o, c, v);
+}
+
 // After a block: recompute every output whose window intersects a column's loud
 // row range and really holds a loud element (all threads; out of line).
+template <bool DITHER = false>
 __device__ __forceinline__ void hxsFixup(HxsArgsP xp, int b, const int* loudLo, const int* loudHi) {
     const SrcDesc src = kload(&xp->src);
     const OutDesc od = kload(&xp->od);
@@ -178,7 +197,7 @@ __device__ __forceinline__ void hxsFixup(HxsArgsP xp, int b, const int* loudLo, 
             const int64_t t0 = a * Qc + xp->rowOff[r];
             bool loud = false;
             for (int kk = 0; kk < w1 - w0 && !loud; ++kk) loud = hxLoud(srcRead<float>(src, t0 + kk, c));
-            if (loud) outWrite<float>(od, o, c, static_cast<float>(hxsExact(xp, a, r, c)));
+            if (loud) hxsOutWrite<DITHER>(od, o, c, static_cast<float>(hxsExact(xp, a, r, c)));
         }
     }
 }
@@ -521,8 +540,9 @@ __device__ __forceinline__ int32_t pcm16Of(float y) {
 // (one 16-B store), 2 stereo-interleaved f32 (lane pairs swap halves by DPP: one 16-B store of two
 // frames each), 3 f64 (4 stores), 4 stereo-interleaved PCM16 (two int16 frames, 8 B), 5 stereo-
 // interleaved f16 / bf16 (two frames, 8 B: the same lane-pair swap, packed f32 -> half conversion).
-template <int VST>
-__device__ __forceinline__ void hxsStoreFast(const HxsArgs& x, char* p, f32x4 y, int lane) {
+// DITHER (VST 4): the dithered quantizer, pos = the stream position of the first frame at p.
+template <int VST, bool DITHER = false>
+__device__ __forceinline__ void hxsStoreFast(const HxsArgs& x, char* p, f32x4 y, int lane, int64_t pos = 0) {
     const bool nt = kHxsDev && x.nt;
     if (VST == 2 || VST == 4 || VST == 5) {
         const bool even = (lane & 1) == 0;
@@ -533,7 +553,25 @@ __device__ __forceinline__ void hxsStoreFast(const HxsArgs& x, char* p, f32x4 y,
         if (even) { w[0] = y[0]; w[1] = q0; w[2] = y[1]; w[3] = q1; }
         else      { w[0] = q0; w[1] = y[2]; w[2] = q1; w[3] = y[3]; }
         if constexpr (VST == 4) {  // two int16 stereo frames (8 B): clamp, x32767, truncate (main.go:497-541)
-            const int32_t i0 = pcm16Of(w[0]), i1 = pcm16Of(w[1]), i2 = pcm16Of(w[2]), i3 = pcm16Of(w[3]);
+            int32_t i0, i1, i2, i3;
+            if constexpr (DITHER) {  // after the lane-pair swap: w[0], w[1] = channels 0, 1 of frame pos; w[2], w[3] of pos + 1
+                const uint64_t n0 = static_cast<uint64_t>(pos), n1 = n0 + 1;
+                const uint32_t key0 = ditherKey(x.dseedLo, x.dseedHi, 0), key1 = ditherKey(x.dseedLo, x.dseedHi, 1);  // uniform
+                const uint32_t h0 = static_cast<uint32_t>(n0 >> 32), h1 = static_cast<uint32_t>(n1 >> 32);
+                const uint32_t ka = ditherKeyHi(key0, h0), kb = ditherKeyHi(key1, h0);
+                uint32_t kc = ka, kd = kb;
+                if (h1 != h0) {  // the pair straddles a multiple of 2^32
+                    kc = ditherKeyHi(key0, h1);
+                    kd = ditherKeyHi(key1, h1);
+                }
+                const uint32_t l0 = static_cast<uint32_t>(n0), l1 = static_cast<uint32_t>(n1);
+                i0 = pcmDitherOfF64(static_cast<double>(w[0]), 16, ditherNoise(ka, l0));
+                i1 = pcmDitherOfF64(static_cast<double>(w[1]), 16, ditherNoise(kb, l0));
+                i2 = pcmDitherOfF64(static_cast<double>(w[2]), 16, ditherNoise(kc, l1));
+                i3 = pcmDitherOfF64(static_cast<double>(w[3]), 16, ditherNoise(kd, l1));
+            } else {
+                i0 = pcm16Of(w[0]); i1 = pcm16Of(w[1]); i2 = pcm16Of(w[2]); i3 = pcm16Of(w[3]);
+            }
             uint2 v;
             v.x = (static_cast<uint32_t>(i0) & 0xffffu) | (static_cast<uint32_t>(i1) << 16);
             v.y = (static_cast<uint32_t>(i2) & 0xffffu) | (static_cast<uint32_t>(i3) << 16);
@@ -661,7 +699,7 @@ __device__ __forceinline__ void hxsRegConvert(XP x, const HxsStage& st, bool fas
 // stored row block ("fast": the common case -- all but the launch's edge blocks); then the
 // epilogue of a period is scale + (stereo) lane swap + one 16-B store at a pointer advanced by a
 // constant per period, with no per-period range checks or 64-bit index arithmetic.
-template <int NS, int VST, bool FAST>
+template <int NS, int VST, bool FAST, bool DITHER>
 __device__ __forceinline__ void hxsGroups(const HxsArgs& x, const HxsShared& sh_, int lane, const h8v (&Ah)[NS],
                                           const h8v (&Al)[NS], uint32_t laneOff, int u0, int P, int nslot,
                                           char* obase, int64_t pstride, int64_t aCol, int64_t oRow0, bool colOk,
@@ -677,21 +715,24 @@ __device__ __forceinline__ void hxsGroups(const HxsArgs& x, const HxsShared& sh_
         if constexpr (FAST) {
             // periods past the chunk (ngroups * G > Np) belong to the next chunk's column, whose
             // fixup owns their loud outputs: storing them here raced with it (r05 loud sweep, C=3)
-            if (p < x.Np) hxsStoreFast<VST>(x, obase + static_cast<int64_t>(p) * pstride, y, lane);
+            if (p < x.Np) hxsStoreFast<VST, DITHER>(x, obase + static_cast<int64_t>(p) * pstride, y, lane, (aCol + p) * x.Pc + oRow0 + ((lane & 1) ? 2 : 0) + x.dpos);
         } else {
             const int64_t a = aCol + p;
             const int64_t o0 = a * x.Pc + oRow0;
             const bool live = colOk && p < x.Np && a < x.a_hi;
             if (fullRb && live && (!x.out_pcm || VST == 4 || VST == 5) && a * x.Pc >= x.o_lo && (a + 1) * x.Pc <= x.o_hi) {
                 char* pp = x.out + (o0 + (((VST == 2 || VST == 4 || VST == 5) && (lane & 1)) ? 2 : 0)) * x.out_fs + ((VST == 2 || VST == 4 || VST == 5) ? 0 : ccol * x.out_cs);
-                hxsStoreFast<VST>(x, pp, y, lane);
+                hxsStoreFast<VST, DITHER>(x, pp, y, lane, o0 + ((lane & 1) ? 2 : 0) + x.dpos);
             } else if (live) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int64_t o = o0 + i;
                     if (oRow0 + i < x.Pc && o >= x.o_lo && o < x.o_hi) {
                         char* pp = x.out + o * x.out_fs + ccol * x.out_cs;
-                        if (x.out_pcm) pcmWrite(pp, 0, x.out_pcm, static_cast<double>(y[i]));
+                        if constexpr (DITHER)  // integer PCM (hxsArgsOf)
+                            pcmWriteDither(pp, 0, x.out_pcm, static_cast<double>(y[i]), x.dseedLo, x.dseedHi, static_cast<uint32_t>(ccol),
+                                           static_cast<uint64_t>(o + x.dpos));
+                        else if (x.out_pcm) pcmWrite(pp, 0, x.out_pcm, static_cast<double>(y[i]));
                         else if (x.out_f64) *reinterpret_cast<double*>(pp) = static_cast<double>(y[i]);
                         else *reinterpret_cast<float*>(pp) = y[i];
                     }
@@ -776,7 +817,7 @@ __device__ __forceinline__ void hxsGroups(const HxsArgs& x, const HxsShared& sh_
     }
 }
 
-template <int NS, int VST>
+template <int NS, int VST, bool DITHER>
 __device__ __forceinline__ void hxsCompute(const HxsArgs& x, const HxsShared& sh_, int wt, int lane) {
     const uint32_t QS = sh_.QS;
     const int GQ = x.G * x.Qc;
@@ -822,16 +863,16 @@ __device__ __forceinline__ void hxsCompute(const HxsArgs& x, const HxsShared& sh
         char* obase = x.out + (aCol * x.Pc + oRow0 + (((VST == 2 || VST == 4 || VST == 5) && (lane & 1)) ? 2 : 0)) * x.out_fs +
                       ((VST == 2 || VST == 4 || VST == 5) ? 0 : ccol * x.out_cs);
         if (__builtin_amdgcn_ballot_w64(!laneFast) == 0)
-            hxsGroups<NS, VST, true>(x, sh_, lane, Ah, Al, laneOff, u0, P, nslot, obase, pstride, aCol, oRow0, colOk,
+            hxsGroups<NS, VST, true, DITHER>(x, sh_, lane, Ah, Al, laneOff, u0, P, nslot, obase, pstride, aCol, oRow0, colOk,
                                      ccol, fullRb, tm, tw);
         else
-            hxsGroups<NS, VST, false>(x, sh_, lane, Ah, Al, laneOff, u0, P, nslot, obase, pstride, aCol, oRow0, colOk,
+            hxsGroups<NS, VST, false, DITHER>(x, sh_, lane, Ah, Al, laneOff, u0, P, nslot, obase, pstride, aCol, oRow0, colOk,
                                       ccol, fullRb, tm, tw);
         if (kHxsDev && x.prof && bi == static_cast<int>(blockIdx.x)) tSteps = __builtin_amdgcn_s_memtime();
         if (*sh_.flag) {  // uniform (LDS after the barrier; reset only after the barrier below)
             __builtin_amdgcn_s_waitcnt(0);  // this wave's output stores landed
             __syncthreads();
-            hxsFixup(hxsCold(), b, sh_.loudLo, sh_.loudHi);
+            hxsFixup<DITHER>(hxsCold(), b, sh_.loudLo, sh_.loudHi);
             __syncthreads();  // every wave's fixup read loudLo/loudHi before the next block resets them
         }
     }
@@ -872,7 +913,7 @@ __device__ __forceinline__ void hxsHistKeep(const HxsArgs& x, int64_t me, int64_
 // Loader wave l: same barrier sequence as the compute
 // waves; in step j it converts load j (issued kHxsD steps earlier) into the ring
 // and issues load j + kHxsD into the registers just freed.
-template <int FMT>
+template <int FMT, bool DITHER>
 __device__ __forceinline__ void hxsRegLoadersT(const HxsArgs& x, const HxsShared& sh_, int l, int lane) {
     // Every argument is read through an opaque kernarg pointer renewed per step (hxsCold), so
     // the scalar loads sit next to their uses instead of pinning ~70 SGPRs for the whole
@@ -926,27 +967,28 @@ __device__ __forceinline__ void hxsRegLoadersT(const HxsArgs& x, const HxsShared
         if (*sh_.flag) {  // same sequence as the compute waves
             __builtin_amdgcn_s_waitcnt(0);
             __syncthreads();
-            hxsFixup(hxsCold(), b, sh_.loudLo, sh_.loudHi);
+            hxsFixup<DITHER>(hxsCold(), b, sh_.loudLo, sh_.loudHi);
             __syncthreads();
         }
     }
 }
 
+template <bool DITHER>
 __device__ __forceinline__ void hxsRegLoaders(const HxsArgs& x, const HxsShared& sh_, int l, int lane) {
 #ifdef GAR_HXS_ONLYFMT  // development: one loader format per build (register-allocation studies)
-    hxsRegLoadersT<GAR_HXS_ONLYFMT>(x, sh_, l, lane);
+    hxsRegLoadersT<GAR_HXS_ONLYFMT, DITHER>(x, sh_, l, lane);
     return;
 #endif
-    if (x.fmt == 1) hxsRegLoadersT<1>(x, sh_, l, lane);
-    else if (x.fmt == 2) hxsRegLoadersT<2>(x, sh_, l, lane);
-    else if (x.fmt == 3) hxsRegLoadersT<3>(x, sh_, l, lane);
-    else if (x.fmt == 4) hxsRegLoadersT<4>(x, sh_, l, lane);
-    else if (x.fmt == 6) hxsRegLoadersT<6>(x, sh_, l, lane);
-    else if (x.fmt == 7) hxsRegLoadersT<7>(x, sh_, l, lane);
-    else hxsRegLoadersT<0>(x, sh_, l, lane);
+    if (x.fmt == 1) hxsRegLoadersT<1, DITHER>(x, sh_, l, lane);
+    else if (x.fmt == 2) hxsRegLoadersT<2, DITHER>(x, sh_, l, lane);
+    else if (x.fmt == 3) hxsRegLoadersT<3, DITHER>(x, sh_, l, lane);
+    else if (x.fmt == 4) hxsRegLoadersT<4, DITHER>(x, sh_, l, lane);
+    else if (x.fmt == 6) hxsRegLoadersT<6, DITHER>(x, sh_, l, lane);
+    else if (x.fmt == 7) hxsRegLoadersT<7, DITHER>(x, sh_, l, lane);
+    else hxsRegLoadersT<0, DITHER>(x, sh_, l, lane);
 }
 
-template <int NS, int VST>
+template <int NS, int VST, bool DITHER = false>
 __global__ __launch_bounds__(64 * kHxsWaves) void hxs_kernel(HxsArgs x) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     HxsShared s;
@@ -968,8 +1010,8 @@ __global__ __launch_bounds__(64 * kHxsWaves) void hxs_kernel(HxsArgs x) {
     // buffer of the double-buffered history, so it never aliases what this launch reads).  Small
     // launches: the loader waves copy it while the compute waves run their MFMAs (the loaders' only
     // other work is the one-pass window gather); otherwise every thread after its role.
-    if (wt < x.nprog) hxsCompute<NS, VST>(x, s, wt, lane);
-    else hxsRegLoaders(x, s, wt - x.nprog, lane);
+    if (wt < x.nprog) hxsCompute<NS, VST, DITHER>(x, s, wt, lane);
+    else hxsRegLoaders<DITHER>(x, s, wt - x.nprog, lane);
     if (x.hn > 0 && !x.small) hxsHistKeep(x, static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x,
                                           static_cast<int64_t>(gridDim.x) * blockDim.x);
 }
@@ -977,7 +1019,7 @@ __global__ __launch_bounds__(64 * kHxsWaves) void hxs_kernel(HxsArgs x) {
 // One compute wave of a small launch (one macro period per column): NS steps of 3 MFMAs over the
 // window image from LDS address aH (hi plane; lo plane at + dL), scale, store row block rbw of
 // block b's 16 columns.  Shared by hxs_small_kernel and hxq_kernel: identical bits.
-template <int NS, int VST>
+template <int NS, int VST, bool DITHER>
 __device__ __forceinline__ void hxsSmallOut(const HxsArgs& x, uint32_t aH, uint32_t dL, const h8v* Ah, const h8v* Al, int b,
                                             int rbw, int lane, int sh) {
     const int grp = lane >> 4, l16 = lane & 15;
@@ -1004,14 +1046,17 @@ __device__ __forceinline__ void hxsSmallOut(const HxsArgs& x, uint32_t aH, uint3
     if (fullRb && live && (!x.out_pcm || VST == 4 || VST == 5) && a * x.Pc >= x.o_lo && (a + 1) * x.Pc <= x.o_hi) {
         char* pp = x.out + (o0 + (((VST == 2 || VST == 4 || VST == 5) && (lane & 1)) ? 2 : 0)) * x.out_fs +
                    ((VST == 2 || VST == 4 || VST == 5) ? 0 : ccol * x.out_cs);
-        hxsStoreFast<VST>(x, pp, y, lane);
+        hxsStoreFast<VST, DITHER>(x, pp, y, lane, o0 + ((lane & 1) ? 2 : 0) + x.dpos);
     } else if (live) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int64_t o = o0 + i;
             if (oRow0 + i < x.Pc && o >= x.o_lo && o < x.o_hi) {
                 char* pp = x.out + o * x.out_fs + ccol * x.out_cs;
-                if (x.out_pcm) pcmWrite(pp, 0, x.out_pcm, static_cast<double>(y[i]));
+                if constexpr (DITHER)  // integer PCM (hxsArgsOf)
+                    pcmWriteDither(pp, 0, x.out_pcm, static_cast<double>(y[i]), x.dseedLo, x.dseedHi, static_cast<uint32_t>(ccol),
+                                   static_cast<uint64_t>(o + x.dpos));
+                else if (x.out_pcm) pcmWrite(pp, 0, x.out_pcm, static_cast<double>(y[i]));
                 else if (x.out_f64) *reinterpret_cast<double*>(pp) = static_cast<double>(y[i]);
                 else *reinterpret_cast<float*>(pp) = y[i];
             }
@@ -1026,7 +1071,7 @@ __device__ __forceinline__ void hxsSmallOut(const HxsArgs& x, uint32_t aH, uint3
 // Same window image, same A fragments, same MFMA order and epilogue as hxs_kernel: identical bits.
 //   all waves: gather the block's window [0, Wg) into the image (hxsSmallStage) | barrier |
 //   wave w < nprog: row block w, NS steps of 3 MFMAs, scale, store | loud fixup | history keep.
-template <int NS, int VST>
+template <int NS, int VST, bool DITHER = false>
 __global__ __launch_bounds__(64 * kHxRbMaxWaves) void hxs_small_kernel(HxsArgs x) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t QS = 16u * static_cast<uint32_t>(x.Rt) + 64u;
@@ -1078,12 +1123,12 @@ __global__ __launch_bounds__(64 * kHxRbMaxWaves) void hxs_small_kernel(HxsArgs x
             hxsSmallStage(&x, b, static_cast<int>(threadIdx.x), static_cast<int>(blockDim.x), ring, QS, loudLo, loudHi, flag);
         __syncthreads();  // the whole window in the image
         if (comp)
-            hxsSmallOut<NS, VST>(x, static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_s4p)(ring + laneOff))) + 8u * static_cast<uint32_t>(u0),
+            hxsSmallOut<NS, VST, DITHER>(x, static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_s4p)(ring + laneOff))) + 8u * static_cast<uint32_t>(u0),
                                  dL, Ah, Al, b, rbw, lane, sh);
         if (*flag) {  // uniform (LDS after the barrier)
             __builtin_amdgcn_s_waitcnt(0);
             __syncthreads();
-            hxsFixup(hxsCold(), b, loudLo, loudHi);
+            hxsFixup<DITHER>(hxsCold(), b, loudLo, loudHi);
         }
         __syncthreads();  // every wave done with the image / loud state before the next block
     }
@@ -1145,6 +1190,7 @@ __device__ __forceinline__ void hxqPut(char* ring, uint32_t QS, uint32_t Rt, int
 
 // hxsFixup restricted to output rows [r0, r1) of each period (the workgroup's row blocks: another
 // workgroup owns -- and stores -- the other rows).
+template <bool DITHER>
 __device__ __forceinline__ void hxqFixup(HxsArgsP xp, int b, const int* loudLo, const int* loudHi, int r0, int r1) {
     const SrcDesc src = kload(&xp->src);
     const OutDesc od = kload(&xp->od);
@@ -1170,12 +1216,12 @@ __device__ __forceinline__ void hxqFixup(HxsArgsP xp, int b, const int* loudLo, 
             const int64_t t0 = a * Qc + xp->rowOff[r];
             bool loud = false;
             for (int kk = 0; kk < w1 - w0 && !loud; ++kk) loud = hxLoud(srcRead<float>(src, t0 + kk, c));
-            if (loud) outWrite<float>(od, o, c, static_cast<float>(hxsExact(xp, a, r, c)));
+            if (loud) hxsOutWrite<DITHER>(od, o, c, static_cast<float>(hxsExact(xp, a, r, c)));
         }
     }
 }
 
-template <int NS, int VST>
+template <int NS, int VST, bool DITHER = false>
 __global__ __launch_bounds__(64 * kHxqMaxWaves) void hxq_kernel(HxsArgs x) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t Rt = static_cast<uint32_t>(x.Rt), QS = 16u * Rt + 64u;
@@ -1389,13 +1435,13 @@ __global__ __launch_bounds__(64 * kHxqMaxWaves) void hxq_kernel(HxsArgs x) {
     if (comp) {
         const int grp = lane >> 4, l16 = lane & 15;
         const uint32_t laneOff = (l16 & 3) * QS + 8u * (4 * grp + (l16 >> 2));
-        hxsSmallOut<NS, VST>(x, static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_s4p)(ring + laneOff))) + 8u * static_cast<uint32_t>(u0 - lo),
+        hxsSmallOut<NS, VST, DITHER>(x, static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_s4p)(ring + laneOff))) + 8u * static_cast<uint32_t>(u0 - lo),
                              8u * Rt, Ah, Al, b, rbw, lane, -(x.ea + kHxXs));
     }
     if (*flag) {  // uniform (LDS after the barrier)
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
-        hxqFixup(hxsCold(), b, loudLo, loudHi, 16 * r0, 16 * (r0 + nrw));
+        hxqFixup<DITHER>(hxsCold(), b, loudLo, loudHi, 16 * r0, 16 * (r0 + nrw));
     }
     const unsigned long long tOut = (kHxsDev && x.prof) ? __builtin_amdgcn_s_memtime() : 0;
     if (x.hn > 0) {
@@ -1418,22 +1464,32 @@ __global__ __launch_bounds__(64 * kHxqMaxWaves) void hxq_kernel(HxsArgs x) {
     }
 }
 
-template <int NS, int VST>
-hipError_t hxsLaunch(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, int qWaves) {
+template <int NS, int VST, bool DITHER>
+hipError_t hxsLaunchT(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, int qWaves) {
     if (x.small && x.qGroups > 0) {  // hxq_kernel: (block, row-block group) workgroups
-        if (const size_t lim_ = setMaxLdsOnce(reinterpret_cast<const void*>(&hxq_kernel<NS, VST>)); lim_ < lds) return ldsTooBig("hxq_kernel", lds, lim_);
+        if (const size_t lim_ = setMaxLdsOnce(reinterpret_cast<const void*>(&hxq_kernel<NS, VST, DITHER>)); lim_ < lds) return ldsTooBig("hxq_kernel", lds, lim_);
         const int nw = std::min(kHxqMaxWaves, std::max(std::max(qWaves, 1), x.qRbs));  // waves per workgroup (HxsKnobs::hxqW)
-        hipLaunchKernelGGL((hxq_kernel<NS, VST>), dim3(static_cast<unsigned>(blocks * x.qGroups)), dim3(64 * nw), lds, st, x);
+        hipLaunchKernelGGL((hxq_kernel<NS, VST, DITHER>), dim3(static_cast<unsigned>(blocks * x.qGroups)), dim3(64 * nw), lds, st, x);
         return hipGetLastError();
     }
     if (x.small && !x.bigSmall) {
-        if (const size_t lim_ = setMaxLdsOnce(reinterpret_cast<const void*>(&hxs_small_kernel<NS, VST>)); lim_ < lds) return ldsTooBig("hxs_small_kernel", lds, lim_);
-        hipLaunchKernelGGL((hxs_small_kernel<NS, VST>), dim3(static_cast<unsigned>(blocks)), dim3(64 * x.nprog), lds, st, x);
+        if (const size_t lim_ = setMaxLdsOnce(reinterpret_cast<const void*>(&hxs_small_kernel<NS, VST, DITHER>)); lim_ < lds) return ldsTooBig("hxs_small_kernel", lds, lim_);
+        hipLaunchKernelGGL((hxs_small_kernel<NS, VST, DITHER>), dim3(static_cast<unsigned>(blocks)), dim3(64 * x.nprog), lds, st, x);
         return hipGetLastError();
     }
-    if (const size_t lim_ = setMaxLdsOnce(reinterpret_cast<const void*>(&hxs_kernel<NS, VST>)); lim_ < lds) return ldsTooBig("hxs_kernel", lds, lim_);
-    hipLaunchKernelGGL((hxs_kernel<NS, VST>), dim3(static_cast<unsigned>(blocks)), dim3(64 * (x.nprog + kHxsLoaders)), lds, st, x);
+    if (const size_t lim_ = setMaxLdsOnce(reinterpret_cast<const void*>(&hxs_kernel<NS, VST, DITHER>)); lim_ < lds) return ldsTooBig("hxs_kernel", lds, lim_);
+    hipLaunchKernelGGL((hxs_kernel<NS, VST, DITHER>), dim3(static_cast<unsigned>(blocks)), dim3(64 * (x.nprog + kHxsLoaders)), lds, st, x);
     return hipGetLastError();
+}
+template <int NS, int VST>
+hipError_t hxsLaunch(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, int qWaves) {
+    return hxsLaunchT<NS, VST, false>(x, lds, blocks, st, qWaves);
+}
+// A launch with dither on (HxsArgs::dither; the store layouts that take integer PCM: VST 0 and 4): the DITHER
+// instantiations of the three kernels, a build unit of their own (gar_hxs_i4.hip), so the others carry no dither code.
+template <int NS, int VST>
+hipError_t hxsLaunchDither(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, int qWaves) {
+    return hxsLaunchT<NS, VST, true>(x, lds, blocks, st, qWaves);
 }
 
 #define GAR_HXS_FOR4(M, NS) M(NS, 0) M(NS, 1) M(NS, 2) M(NS, 3) M(NS, 4)
@@ -1452,5 +1508,12 @@ hipError_t hxsLaunch(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t s
 #endif
 #define GAR_HXS_FOR_ALL(M) GAR_HXS_FOR_LO(M) GAR_HXS_FOR_HI(M) GAR_HXS_FOR_HALF(M)
 #define GAR_HXS_INST(NS, V) template hipError_t hxsLaunch<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t, int);
+#if GAR_HXS_QUICK
+#define GAR_HXS_FOR_DITHER(M) M(9, 0) M(9, 4) M(10, 0) M(10, 4)
+#else
+#define GAR_HXS_FOR_DITHER(M) M(1, 0) M(1, 4) M(2, 0) M(2, 4) M(3, 0) M(3, 4) M(4, 0) M(4, 4) M(5, 0) M(5, 4) \
+                              M(6, 0) M(6, 4) M(7, 0) M(7, 4) M(8, 0) M(8, 4) M(9, 0) M(9, 4) M(10, 0) M(10, 4)
+#endif
+#define GAR_HXS_INST_DITHER(NS, V) template hipError_t hxsLaunchDither<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t, int);
 
 }  // namespace gar

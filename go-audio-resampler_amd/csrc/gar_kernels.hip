@@ -112,6 +112,9 @@ hipError_t launchBg(const BgDev& p, const SrcDesc& src, const OutDesc& od, int C
     const int ncu = deviceCUs();
     const FirKnobs k = firLaunchKnobs();
     const FirLaunchPlan pl = firPlanLaunch(p, src, od, C, ncu, k, hc && hc->dst, hc ? hc->n : 0);
+    // a dithered PCM view is stored by the streaming kernels only (the engine fuses PCM where their planner never
+    // declines, hxsPlanFits): any other route would truncate silently
+    if (od.dither && pl.path != FirPath::Hxs) return hipErrorNotSupported;
     switch (pl.path) {
         case FirPath::Bg: return launchBgPlan(pl.bg, k.bg, p, src, od, stream, hc);
         case FirPath::Hxs: return launchHxsPlan(pl.hxs, k.hxs, *p.hx, src, od, C, stream, hc);
@@ -519,7 +522,7 @@ hipError_t launchCopy(const void* src, int src_f64, int64_t s_fs, int64_t s_cs, 
 }
 
 __global__ __launch_bounds__(256) void convert_kernel(const void* s, int st, int64_t sfs, int64_t scs, void* d, int dt,
-                                                      int64_t dfs, int64_t dcs, int64_t n, int C) {
+                                                      int64_t dfs, int64_t dcs, int64_t n, int C, Dither dz) {
     const int64_t total = n * C;
     for (int64_t idx = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; idx < total;
          idx += static_cast<int64_t>(gridDim.x) * blockDim.x) {
@@ -528,7 +531,9 @@ __global__ __launch_bounds__(256) void convert_kernel(const void* s, int st, int
         const int64_t se = t * sfs + c * scs, de = t * dfs + c * dcs;
         const double v = st >= kSampF16 ? pcmRead(s, se, st)
                                   : (st == 1 ? static_cast<const double*>(s)[se] : static_cast<double>(static_cast<const float*>(s)[se]));
-        if (dt >= kSampF16) pcmWrite(d, de, dt, v);  // half: one rounding from f64
+        if (dz.mode && pcmIsInt(dt))
+            pcmWriteDither(d, de, dt, v, dz.seedLo, dz.seedHi, static_cast<uint32_t>(c), static_cast<uint64_t>(dz.pos0 + t));
+        else if (dt >= kSampF16) pcmWrite(d, de, dt, v);  // half: one rounding from f64
         else if (dt == 1) static_cast<double*>(d)[de] = v;
         else static_cast<float*>(d)[de] = static_cast<float>(v);
     }
@@ -565,15 +570,24 @@ __global__ __launch_bounds__(256) void unpack24_kernel(const uint8_t* s, T* d, i
     }
 }
 
-template <class T>
-__global__ __launch_bounds__(256) void pack24_kernel(const T* s, uint8_t* d, int64_t total) {
+// DITHER: sample e = t * C + c is quantized by pcmDitherAt at stream position dz.pos0 + t of channel c (quads and tail).
+template <class T, bool DITHER>
+__global__ __launch_bounds__(256) void pack24_kernel(const T* s, uint8_t* d, int64_t total, int C, Dither dz) {
     typedef T tx2 __attribute__((ext_vector_type(2)));
     typedef T tx4 __attribute__((ext_vector_type(4)));
     const int64_t nq = total >> 2;
     for (int64_t q = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; q <= nq;
          q += static_cast<int64_t>(gridDim.x) * blockDim.x) {
         if (q == nq) {  // checked tail
-            for (int64_t e = 4 * nq; e < total; ++e) pcmWrite(d, e, kSampPcm24P, static_cast<double>(s[e]));
+            for (int64_t e = 4 * nq; e < total; ++e) {
+                if constexpr (DITHER) {
+                    const int64_t t = e / C;
+                    pcmWriteDither(d, e, kSampPcm24P, static_cast<double>(s[e]), dz.seedLo, dz.seedHi,
+                                   static_cast<uint32_t>(e - t * C), static_cast<uint64_t>(dz.pos0 + t));
+                } else {
+                    pcmWrite(d, e, kSampPcm24P, static_cast<double>(s[e]));
+                }
+            }
             break;
         }
         T y[4];
@@ -586,7 +600,15 @@ __global__ __launch_bounds__(256) void pack24_kernel(const T* s, uint8_t* d, int
         }
         int32_t i[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) i[k] = pcmOfF64(static_cast<double>(y[k]), 24);
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (DITHER) {
+                const int64_t e = 4 * q + k, t = e / C;
+                i[k] = pcmDitherAt(static_cast<double>(y[k]), 24, dz.seedLo, dz.seedHi, static_cast<uint32_t>(e - t * C),
+                                   static_cast<uint64_t>(dz.pos0 + t));
+            } else {
+                i[k] = pcmOfF64(static_cast<double>(y[k]), 24);
+            }
+        }
         uint32_t w[3];
         pcm24Pack4(i, w);
         *reinterpret_cast<u32x3a*>(d + 12 * q) = u32x3a{w[0], w[1], w[2]};
@@ -594,7 +616,7 @@ __global__ __launch_bounds__(256) void pack24_kernel(const T* s, uint8_t* d, int
 }
 
 hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs, void* dst, int d_type, int64_t d_fs,
-                         int64_t d_cs, int64_t n, int C, hipStream_t stream) {
+                         int64_t d_cs, int64_t n, int C, hipStream_t stream, const Dither& dz) {
     if (n <= 0) return hipSuccess;
     // packed 24-bit, interleaved contiguous from a 4-byte aligned base, against contiguous f32 / f64 (16-B aligned):
     // the vector kernels (knob GAR_PACK24_VEC=0, read per launch for A/B timing: the per-element kernel)
@@ -613,15 +635,17 @@ hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs
             uint8_t* dp = static_cast<uint8_t*>(dst);
             if (unpackV && d_type == 1) hipLaunchKernelGGL(unpack24_kernel<double>, g, b, 0, stream, sp, static_cast<double*>(dst), total);
             else if (unpackV) hipLaunchKernelGGL(unpack24_kernel<float>, g, b, 0, stream, sp, static_cast<float*>(dst), total);
-            else if (s_type == 1) hipLaunchKernelGGL(pack24_kernel<double>, g, b, 0, stream, static_cast<const double*>(src), dp, total);
-            else hipLaunchKernelGGL(pack24_kernel<float>, g, b, 0, stream, static_cast<const float*>(src), dp, total);
+            else if (s_type == 1 && dz.mode) hipLaunchKernelGGL((pack24_kernel<double, true>), g, b, 0, stream, static_cast<const double*>(src), dp, total, C, dz);
+            else if (s_type == 1) hipLaunchKernelGGL((pack24_kernel<double, false>), g, b, 0, stream, static_cast<const double*>(src), dp, total, C, dz);
+            else if (dz.mode) hipLaunchKernelGGL((pack24_kernel<float, true>), g, b, 0, stream, static_cast<const float*>(src), dp, total, C, dz);
+            else hipLaunchKernelGGL((pack24_kernel<float, false>), g, b, 0, stream, static_cast<const float*>(src), dp, total, C, dz);
             return hipGetLastError();
         }
     }
     int64_t blocks = (n * C + 255) / 256;
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(convert_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, src, s_type, s_fs, s_cs,
-                       dst, d_type, d_fs, d_cs, n, C);
+                       dst, d_type, d_fs, d_cs, n, C, dz);
     return hipGetLastError();
 }
 

@@ -36,6 +36,12 @@ struct OutDesc {
                            // (3 bytes per sample; fs / cs count samples) or 4 / 5: f16 / bf16 (RNE)
     int64_t o_lo, o_hi;
     int* err;              // the calling handle's device status word (host-mapped), null if none
+    // TPDF dither of an integer PCM store (gar.h gar_set_dither; ditherNoise below): mode 0 truncates as ever.
+    // dpos0 = position in the handle's output stream of output o0 (the view's base), so output o has o - o0 + dpos0
+    // whichever launch of a call writes it; channel c of the view is channel c of the handle.
+    int dither;
+    uint32_t dseedLo, dseedHi;
+    int64_t dpos0;
 };
 
 // Integer PCM <-> float, after cmd/resample-wav/main.go:444-543 (maxInt16/24/32, main.go:54-56):
@@ -86,6 +92,41 @@ __host__ __device__ inline int32_t pcmOfF64(double y, int bits) {
     const double s = v * pcmMax(bits);
     return s == s ? static_cast<int32_t>(s) : 0;
 }
+// TPDF-dithered quantizer (gar.h gar_set_dither).  The noise of a sample is a function of
+// (seed, channel, position in the output stream) alone, through a 32-bit integer hash (wrapping uint32):
+//   key(c)  = h32(lo32(seed) ^ h32(hi32(seed) ^ h32(c + 1)))          per channel
+//   kh      = h32(key(c) + hi32(n))                                   per 2^32 positions
+//   r       = h32(kh ^ lo32(n));  d = ((r & 0xffff) - (r >> 16)) / 65536   in (-1, 1), triangular, exact
+// so a store path hoists key and kh and pays one h32 (two 32-bit multiplies) per sample.
+constexpr int kDitherNone = 0, kDitherTpdf = 1;
+__host__ __device__ inline bool pcmIsInt(int t) { return t >= 16; }  // 16 / 24 / 32 / packed 24: not f32 / f64 / half
+__host__ __device__ inline uint32_t ditherH32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+__host__ __device__ inline uint32_t ditherKey(uint32_t seedLo, uint32_t seedHi, uint32_t c) {
+    return ditherH32(seedLo ^ ditherH32(seedHi ^ ditherH32(c + 1u)));
+}
+__host__ __device__ inline uint32_t ditherKeyHi(uint32_t key, uint32_t nHi) { return ditherH32(key + nHi); }
+__host__ __device__ inline double ditherNoise(uint32_t kh, uint32_t nLo) {
+    const uint32_t r = ditherH32(kh ^ nLo);
+    return static_cast<double>(static_cast<int32_t>(r & 0xffffu) - static_cast<int32_t>(r >> 16)) * (1.0 / 65536.0);
+}
+// floor(clamp(y, -1, 1) * maxVal + (0.5 + d)), clamped to +-maxVal; NaN -> 0: round to nearest with a +-1 LSB
+// triangular dither d (one f64 addition, then floor)
+__host__ __device__ inline int32_t pcmDitherOfF64(double y, int bits, double d) {
+#pragma clang fp contract(off)  // the product rounds before the addition (an f64 sample's product is not exact)
+    const double m = pcmMax(bits);
+    const double v = y > 1.0 ? 1.0 : (y < -1.0 ? -1.0 : y);
+    const double q = __builtin_floor(v * m + (0.5 + d));
+    const double c = q > m ? m : (q < -m ? -m : q);
+    return c == c ? static_cast<int32_t>(c) : 0;
+}
+// The quantizer of one sample from scratch (checked stores, the staged kernels, gar_dev_dither_quantize).
+__host__ __device__ inline int32_t pcmDitherAt(double y, int bits, uint32_t seedLo, uint32_t seedHi, uint32_t c, uint64_t n) {
+    const uint32_t kh = ditherKeyHi(ditherKey(seedLo, seedHi, c), static_cast<uint32_t>(n >> 32));
+    return pcmDitherOfF64(y, bits, ditherNoise(kh, static_cast<uint32_t>(n)));
+}
 // One packed 24-bit sample at byte address b (no alignment): byte-wise, so nothing outside its 3 bytes is touched.
 __host__ __device__ inline int32_t pcm24Load(const uint8_t* b) {
     const uint32_t u = static_cast<uint32_t>(b[0]) | (static_cast<uint32_t>(b[1]) << 8) | (static_cast<uint32_t>(b[2]) << 16);
@@ -130,6 +171,14 @@ __host__ __device__ inline void pcmWrite(void* p, int64_t e, int bits, double y)
     const double s = v * pcmMax(bits);
     if (bits == 16) static_cast<int16_t*>(p)[e] = static_cast<int16_t>(s == s ? static_cast<int32_t>(s) : 0);
     else static_cast<int32_t*>(p)[e] = s == s ? static_cast<int32_t>(s) : 0;
+}
+// pcmWrite of an integer PCM type with the dithered quantizer: sample of channel c at stream position n.
+__host__ __device__ inline void pcmWriteDither(void* p, int64_t e, int bits, double y, uint32_t seedLo, uint32_t seedHi,
+                                               uint32_t c, uint64_t n) {
+    const int32_t i = pcmDitherAt(y, bits, seedLo, seedHi, c, n);
+    if (bits == kSampPcm24P) pcm24Store(static_cast<uint8_t*>(p) + 3 * e, i);
+    else if (bits == 16) static_cast<int16_t*>(p)[e] = static_cast<int16_t>(i);
+    else static_cast<int32_t*>(p)[e] = i;
 }
 
 struct HxDev;
@@ -240,8 +289,14 @@ hipError_t launchCopy(const void* src, int src_f64, int64_t s_fs, int64_t s_cs, 
 // 24-bit (pcmRead / pcmWrite); not the ABI's codes for f32 / f64.  Packed 24-bit against a contiguous f32 / f64
 // buffer runs the vector kernels (unpack24_kernel / pack24_kernel: 4 samples <-> 3 dwords per thread) when the
 // packed side is interleaved-contiguous from a 4-byte aligned base; every other case the per-element kernel.
+// `dz` (mode on, an integer PCM d_type): element (t, c) is stored by the dithered quantizer at stream position dz.pos0 + t.
+struct Dither {
+    int mode = kDitherNone;
+    uint32_t seedLo = 0, seedHi = 0;
+    int64_t pos0 = 0;
+};
 hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs, void* dst, int d_type, int64_t d_fs,
-                         int64_t d_cs, int64_t n, int C, hipStream_t stream);
+                         int64_t d_cs, int64_t n, int C, hipStream_t stream, const Dither& dz = Dither());
 
 // One history of a state snapshot (gar_state_save / gar_state_load): `rows` rows of C elements of `es`
 // bytes, contiguous at `ptr` (leading dimension C, the engine's Hist layout), stored tightly packed from

@@ -92,6 +92,7 @@ EXPORTED = [
     "gar_profile_read", "gar_stage_state", "gar_num_stages", "gar_stage_geometry", "gar_get_statistics",
     "gar_synchronize", "gar_profile_launch_stats", "gar_profile_kinds", "gar_dev_half_convert",
     "gar_dev_pcm24_convert", "gar_dev_hxs_plan", "gar_dev_fir_plan", "gar_state_size", "gar_state_save", "gar_state_load",
+    "gar_set_dither", "gar_get_dither", "gar_dev_dither_quantize",
 ]
 
 _lib = None
@@ -165,6 +166,9 @@ def lib():
         "gar_state_size": (i64, [vp]),
         "gar_state_save": (i32, [vp, vp, i64, C.POINTER(i64)]),
         "gar_state_load": (i32, [vp, vp, i64]),
+        "gar_set_dither": (i32, [vp, i32, C.c_uint64]),
+        "gar_get_dither": (i32, [vp, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(i64)]),
+        "gar_dev_dither_quantize": (i32, [i32, C.c_uint64, i32, i64, vp, i64, vp, vp]),
     }
     ab = os.environ.get("GAR_LIB_PATH") is not None
     for name, (res, args) in sig.items():
@@ -365,6 +369,22 @@ class Resampler:
         blob = bytes(blob)
         _check(lib().gar_state_load(self._h, blob, len(blob)))
 
+    # -- dithered integer PCM output (gar.h gar_set_dither / gar_get_dither) --
+    def set_dither(self, mode, seed=0):
+        """DITHER_TPDF: the integer PCM outputs of process_device / flush_device enqueued from now on are
+        rounded to nearest with a +-1 LSB triangular dither, a function of (seed, channel, position in
+        the output stream) alone; DITHER_NONE (the default): the reference's truncation.  Configuration,
+        not stream state: it survives Reset and load_state.  Float and half outputs and the host-memory
+        calls ignore it."""
+        _check(lib().gar_set_dither(self._h, int(mode), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def get_dither(self):
+        """(mode, seed, position): position = the stream position the next device call starts at
+        (GetStatistics samplesOut), -1 when the channels are not in lockstep."""
+        m, s, p = C.c_int32(0), C.c_uint64(0), C.c_int64(0)
+        _check(lib().gar_get_dither(self._h, C.byref(m), C.byref(s), C.byref(p)))
+        return m.value, s.value, p.value
+
     def num_stages(self):
         return lib().gar_num_stages(self._h)
 
@@ -447,6 +467,7 @@ class Resampler:
 PCM16, PCM24, PCM32 = 16, 24, 32
 F16, BF16 = 4, 5  # device sample types only (gar.h GAR_F16 / GAR_BF16), not compute types
 PCM24_PACKED = 280  # device sample type only (gar.h GAR_PCM24_PACKED): 3 bytes per sample, little-endian
+DITHER_NONE, DITHER_TPDF = 0, 1  # gar.h GAR_DITHER_*
 
 
 def _io_type(dtype, pcm_bits=None):
@@ -518,6 +539,17 @@ def pcm24_convert(x):
     i = np.zeros(x.size, dtype=np.int32)
     _check(lib().gar_dev_pcm24_convert(_p(x), x.size, _p(b), _p(i)))
     return b, i
+
+
+def dither_quantize(y, pcm_bits, seed, channel, position0):
+    """Host run of the kernels' dithered quantizer (gar.h gar_dev_dither_quantize) on the float64 array y, taken
+    as the samples of channel `channel` from stream position position0: (int32 integers stored, float64 noise d)."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    q = np.zeros(y.size, dtype=np.int32)
+    d = np.zeros(y.size, dtype=np.float64)
+    _check(lib().gar_dev_dither_quantize(int(pcm_bits), int(seed) & 0xFFFFFFFFFFFFFFFF, int(channel), int(position0),
+                                         _p(y), y.size, _p(q), _p(d)))
+    return q, d
 
 
 def half_convert(x, half_type):

@@ -232,6 +232,42 @@ int64_t gar_device_flush_size(const gar_resampler *r);
  * is the synchronisation point of the asynchronous *_device entry points. */
 gar_status gar_synchronize(gar_resampler *r);
 
+/* ---- dithered integer PCM output ------------------------------------------ */
+/* By default every integer PCM output (GAR_PCM16 / 24 / 32 / GAR_PCM24_PACKED) is the reference CLI's
+ * int(clamp(y, -1, 1) * maxVal): truncation toward zero.  GAR_DITHER_TPDF replaces it, for the integer
+ * PCM out_dtypes of gar_process_device / gar_flush_device, by round-to-nearest with a +-1 LSB
+ * triangular (TPDF) dither, computed inside the kernels that store the samples.  All integer
+ * arithmetic is uint32, wrapping:
+ *   h32(x):   x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *   key(c)  = h32(lo32(seed) ^ h32(hi32(seed) ^ h32(c + 1)))    c: channel index of the handle
+ *                                                               (batch: stream * channels + ch)
+ *   r(c, n) = h32(h32(key(c) + hi32(n)) ^ lo32(n))              n: uint64 position in the output stream
+ *   d(c, n) = ((r & 0xffff) - (r >> 16)) / 65536                in (-1, 1), exact in float32 / float64
+ *   s = clamp(y, -1, 1) * maxVal   (float64, as without dither);   t = 0.5 + d(c, n)   (exact)
+ *   q = floor(s + t)  (one float64 addition, then floor);  q = clamp(q, -maxVal, +maxVal);  NaN -> 0
+ * and q is stored as without dither (int16 / int32 / 3 bytes).
+ * Position: the first output frame of a device call has n = the lockstep group's GetStatistics
+ * samplesOut at entry to the call, frame k of the call n + k.  So:
+ *   - the noise of a sample depends only on (seed, channel, its index in the output stream): not on
+ *     the chunking, the fused or staged conversion path, the layout, or the kernel or launch that
+ *     wrote it;
+ *   - gar_reset zeroes the counter, so the noise restarts;
+ *   - gar_state_save / gar_state_load carry the counter (GetStatistics), so a resumed stream continues
+ *     bit-identically with dither on; the blob format and version are unchanged;
+ *   - outputs returned by host-memory calls advance the position like any others;
+ *   - known quirk: the engine-path QualityQuick Flush is uncounted (resampler.go:276-279), so positions
+ *     repeat if such a stream is processed again after a flush.
+ * The setting is configuration, not stream state (like the design): it applies to the device calls
+ * enqueued after gar_set_dither (the parameters travel by value in kernel arguments: no
+ * synchronisation), survives gar_reset and gar_state_load, is not in the state blob, and works on
+ * dry-run handles.  GAR_F16 / GAR_BF16 / float outputs and the host-memory entry points ignore it.
+ * gar_set_dither: NULL handle or unknown mode -> GAR_ERR_INVALID_ARGUMENT, nothing changed.
+ * gar_get_dither: each output may be NULL; *position = where the next device call would start, -1
+ * when the channels are not in lockstep. */
+enum { GAR_DITHER_NONE = 0, GAR_DITHER_TPDF = 1 };
+gar_status gar_set_dither(gar_resampler *r, int32_t mode, uint64_t seed);
+gar_status gar_get_dither(const gar_resampler *r, int32_t *mode, uint64_t *seed, int64_t *position);
+
 /* ---- state snapshots (checkpoint / resume / migrate) ---------------------- */
 /* The streaming state of a handle -- every channel group with its channel range, the per-stage
  * counters (history lengths, polyphase position, decimator phase, cubic phase, fused / stage-by-stage
@@ -323,6 +359,14 @@ gar_status gar_dev_half_convert(int32_t half_type, const double *in, int64_t n, 
  * unpacked[i] = those bytes read back as the sign-extended integer (the input conversion before
  * its scaling).  Either output may be NULL.  For tests (CPU suite). */
 gar_status gar_dev_pcm24_convert(const double *in, int64_t n, uint8_t *packed, int32_t *unpacked);
+
+/* The dithered quantizer of gar_set_dither run on the host (no GPU; the kernels use the same
+ * functions): out[i] = the integer stored for in[i] as the sample of channel `channel` at stream
+ * position position0 + i, noise[i] = d(channel, position0 + i).  pcm_type is an integer PCM type
+ * (GAR_PCM24_PACKED gives GAR_PCM24's integers), anything else GAR_ERR_INVALID_ARGUMENT.  out and
+ * noise may each be NULL.  For tests (CPU suite). */
+gar_status gar_dev_dither_quantize(int32_t pcm_type, uint64_t seed, int32_t channel, int64_t position0,
+                                   const double *in, int64_t n, int32_t *out, double *noise);
 
 /* The launch plan of the streaming FIR kernels for one call, computed on the host (no GPU; the
  * planner of every streaming launch, csrc/gar_hxs_launch.hpp): writes the GAR_HX_TRACE line(s) such a launch

@@ -5,7 +5,7 @@
 set -u
 B=${ROCM_LLVM:-/opt/rocm/llvm/bin}
 A_DIR=$1; B_DIR=$2; shift 2
-UNITS=${*:-gar_kernels gar_bg_f32a gar_bg_f32b gar_bg_f64 gar_hx gar_hx_i1 gar_hx_i2 gar_hx_i3 gar_hx_i4 gar_hx_i5 gar_hxs gar_hxs_i1 gar_hxs_i2 gar_hxs_i3 gar_hxt_i1 gar_hxt_i2 gar_hxt_i3}
+UNITS=${*:-gar_kernels gar_bg_f32a gar_bg_f32b gar_bg_f64 gar_hx gar_hx_i1 gar_hx_i2 gar_hx_i3 gar_hx_i4 gar_hx_i5 gar_hxs gar_hxs_i1 gar_hxs_i2 gar_hxs_i3 gar_hxs_i4 gar_hxt_i1 gar_hxt_i2 gar_hxt_i3}
 T=$(mktemp -d)
 rc=0
 code() {  # $1 object, $2 output prefix: 0 extracted, 1 no device code

@@ -65,8 +65,8 @@ __device__ __forceinline__ void outWrite(const OutDesc& o, int64_t idx, int c, T
 // value its band gives with that sample zero, whatever the call boundaries, so chunked == one-shot
 // bit for bit -- and records where it was; after the item's stores, the outputs whose REAL window
 // holds a non-finite sample are recomputed over their real taps in f64 in the reference's order
-// (bgNfFixOne: two stages for DFT x2 (*) polyphase composites, as hxsExact does for the split-f16
-// kernels), which gives the reference's NaN / +-Inf for each of them and touches nothing else.
+// (bgNfFixOne -> firExact below, the recompute the split-f16 kernels use for their loud windows),
+// which gives the reference's NaN / +-Inf for each of them and touches nothing else.
 __device__ __forceinline__ bool bgFinite(double v) { return __builtin_isfinite(v); }
 __device__ __forceinline__ bool bgFinite(float v) { return __builtin_isfinite(v); }
 
@@ -85,6 +85,48 @@ __device__ __forceinline__ T kload(const __attribute__((address_space(4))) T* p)
     __builtin_memcpy(&v, (const T*)p, sizeof(T));
     return v;
 }
+
+// ---- the exact recompute of every x == 0 FIR kernel family ---------------------------------------
+// Output (a, r) of channel c in f64 from the stream itself, over the real taps of its window: the
+// FIR row, or -- when the window holds Inf / NaN and the row is a DFT x2 (*) polyphase composite --
+// the reference's two stages in its order (a DFT output touched by an Inf is +-Inf, their polyphase
+// sum NaN; dft_stage.go:259, polyphase_stage.go:288).  A single-stage FIR's non-finite sum is IEEE
+// order-free.  TC = the family's compute type (the history's element type).  `ex` points at the
+// launch's ExactDev the way the caller's cold path reaches its arguments: a copy taken out of the
+// kernarg segment (bg), or the kernarg segment itself, each field loaded here, where it is used
+// (the split-f16 kernels: &x->ex of their cold pointer).
+// Two policies call it: the bg kernels stage only non-finite samples as 0 and store the value when
+// the window is non-finite (bgNfFixOne); the split-f16 kernels also cannot carry |x| >= kHxLoud and
+// store it for every window holding a loud element (gar_hx.hpp hxFixupBlock, gar_hxs.hpp hxsFixup).
+struct ExactVal {
+    double y;
+    bool nonFinite;  // the real window holds Inf / NaN
+};
+template <class TC, class EX>
+__device__ __forceinline__ ExactVal firExact(EX ex, const SrcDesc& src, int Qc, int64_t a, int r, int c) {
+    const int64_t t = a * Qc + ex->rowOff[r];
+    const int len = ex->rowLen[r];
+    const double* row = ex->rows + static_cast<size_t>(r) * ex->rowMax;
+    double s = 0.0, z = 0.0;
+    for (int k = 0; k < len; ++k) {
+        const double v = static_cast<double>(srcRead<TC>(src, t + k, c));
+        s += row[k] * v;
+        z += v * 0.0;
+    }
+    if (z == z || !ex->twoStage) return {s, z != z};
+    const int ph = ex->rowPh[r], par = ex->rowPar[r], T1 = ex->T1, T2 = ex->T2;
+    const double* pa = ex->polyA + static_cast<size_t>(ph) * T2;
+    double y = 0.0;
+    for (int k2 = 0; k2 < T2; ++k2) {
+        const int q = par + k2;
+        const double* cq = ex->dftC + static_cast<size_t>(q & 1) * T1;
+        double u = 0.0;
+        for (int k1 = 0; k1 < T1; ++k1) u += cq[k1] * static_cast<double>(srcRead<TC>(src, t + (q >> 1) + k1, c));
+        y += pa[k2] * u;
+    }
+    return {y, true};
+}
+
 struct BgArgs;
 typedef const __attribute__((address_space(4))) BgArgs* BgArgsP;
 __device__ __forceinline__ BgArgsP bgCold() {
@@ -165,42 +207,19 @@ __device__ GAR_BG_NF_ATTR void bgNfFixOne(BgArgsP ka, int64_t a, int r, int c) {
     const OutDesc od = kload(&ka->od);
     const int64_t o = a * p.Pc + r;
     if (o < od.o_lo || o >= od.o_hi) return;
-    const int* xi = p.xInfo;
-    const int64_t t = a * p.Qc + xi[r];
-    const int len = xi[p.Pc + r];
-    const double* row = p.xRows + static_cast<size_t>(r) * p.xRowMax;
-    double s = 0.0, z = 0.0;
-    for (int k = 0; k < len; ++k) {
-        const double v = static_cast<double>(srcRead<TC>(src, t + k, c));
-        s += row[k] * v;
-        z += v * 0.0;
-    }
-    if (z == z) return;  // the real window is finite: the MFMA value stands
-    if (p.xTwoStage) {   // u = DFT x2 of the window, then the polyphase row (dft_stage.go:259, polyphase_stage.go:288)
-        const int ph = xi[2 * p.Pc + r], par = xi[3 * p.Pc + r], T1 = p.xT1, T2 = p.xT2;
-        const double* pa = p.xPolyA + static_cast<size_t>(ph) * T2;
-        double y = 0.0;
-        for (int k2 = 0; k2 < T2; ++k2) {
-            const int q = par + k2;
-            const double* cq = p.xDftC + static_cast<size_t>(q & 1) * T1;
-            double u = 0.0;
-            for (int k1 = 0; k1 < T1; ++k1) u += cq[k1] * static_cast<double>(srcRead<TC>(src, t + (q >> 1) + k1, c));
-            y += pa[k2] * u;
-        }
-        s = y;
-    }
-    outWrite<TC>(od, o, c, static_cast<TC>(s));
+    const ExactVal e = firExact<TC>(&p.ex, src, p.Qc, a, r, c);
+    if (e.nonFinite) outWrite<TC>(od, o, c, static_cast<TC>(e.y));  // a finite window: the MFMA value stands
 }
 
 template <class TC>
 __device__ GAR_BG_NF_ATTR void bgNfFixRange(BgArgsP ka, int64_t a0, int na, int r0, int r1, int c, int lo, int hi, int tid,
                                           int nth) {
-    const int Qc = ka->p.Qc, Pc = ka->p.Pc;
-    const int* xi = ka->p.xInfo;
+    const int Qc = ka->p.Qc;
+    const int *off = ka->p.ex.rowOff, *len = ka->p.ex.rowLen;
     const int nr = r1 - r0;
     for (int idx = tid; idx < na * nr; idx += nth) {
         const int i = idx / nr, r = r0 + (idx - i * nr);
-        const int w0 = i * Qc + xi[r], w1 = w0 + xi[Pc + r];
+        const int w0 = i * Qc + off[r], w1 = w0 + len[r];
         if (w1 <= lo || w0 > hi) continue;
         bgNfFixOne<TC>(ka, a0 + i, r, c);
     }
@@ -805,7 +824,7 @@ template <class TC>
 __device__ GAR_BG_NF_ATTR void bgRbFix(BgArgsP ka, int b, int rb, int np, const BgNfRb* nf, int tid, int nth) {
     const int Pc = ka->g.Pc, ncols = ka->g.ncols, C = ka->g.C;
     const int64_t a_lo = ka->g.a_lo;
-    const int* xi = ka->p.xInfo;
+    const int *off = ka->p.ex.rowOff, *len = ka->p.ex.rowLen;
     for (int idx = tid; idx < 256; idx += nth) {
         const int n = idx & 15, r = rb * 16 + (idx >> 4);
         const int col = b * 16 + n;
@@ -813,7 +832,7 @@ __device__ GAR_BG_NF_ATTR void bgRbFix(BgArgsP ka, int b, int rb, int np, const 
         int lo = 0x7fffffff, hi = -1;
         for (int w = 0; w < np; ++w) { lo = min(lo, nf->lo[w][n]); hi = max(hi, nf->hi[w][n]); }
         if (hi < 0) continue;
-        const int w0 = xi[r], w1 = w0 + xi[Pc + r];
+        const int w0 = off[r], w1 = w0 + len[r];
         if (w1 <= lo || w0 > hi) continue;
         bgNfFixOne<TC>(ka, a_lo + col / C, r, col % C);
     }

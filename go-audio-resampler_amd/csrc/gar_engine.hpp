@@ -78,14 +78,15 @@ struct StageRT {
     FirPeriodic compositeFir;
     BgPlan fusedP, dftP, decimP;
     DevBuf fusedA, fusedT, dftA, dftT, decimA, decimT;
-    DevBuf fusedX, dftX, decimX, xBankA, xBankC;  // exact rows of the non-finite fixup (attachExact)
+    struct BgX { DevBuf rows, nfList; } fusedX, dftX, decimX;  // a bg plan's exact rows and fix list (attachExact)
+    DevBuf xBankA, xBankC;  // the two stages' banks of a composite: every plan's exact recompute (uploadExact)
     BgDev fusedD{}, dftD{}, decimD{};
     DevBuf pa, pb, pc, pd, pabcd;
     PolyDev polyD{};
     // split-f16 variants (f32 compute), referenced from the BgDev's .hx
     struct HxRT {
         HxPlan plan;
-        DevBuf A, T, rows, rowInfo, banks, banks2, fix;
+        DevBuf A, T, X, fix;  // X: the plan's exact rows (uploadExact)
         HxDev d{};
     } fusedH, dftH, decimH;
 

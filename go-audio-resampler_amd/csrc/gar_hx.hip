@@ -71,17 +71,7 @@ hipError_t launchHxPlan(const HxLaunchPlan& pl, const HxKnobs& k, const HxDev& p
     x.fmt = pl.fmt;
     x.src = src;
     x.od = od;
-    x.rows = p.rows;
-    x.rowOff = p.rowOff;
-    x.rowLen = p.rowLen;
-    x.rowMax = p.rowMax;
-    x.twoStage = p.twoStage;
-    x.rowPh = p.rowPh;
-    x.rowPar = p.rowPar;
-    x.polyA = p.polyA;
-    x.dftC = p.dftC;
-    x.T1 = p.T1;
-    x.T2 = p.T2;
+    x.ex = p.ex;
     x.ib0 = pl.ib0;
     x.ib1 = pl.ib1;
     x.fix = p.fix;

@@ -76,16 +76,7 @@ struct HxArgs {
     // cold fields (edge gathers, exact fallback of loud outputs)
     SrcDesc src;
     OutDesc od;
-    const double* rows;    // [Pc][rowMax] the FIR rows in f64
-    const int* rowOff;     // [Pc] window offset of row r within its macro period
-    const int* rowLen;     // [Pc]
-    int rowMax;
-    int twoStage;          // rows are DFT x2 (*) polyphase composites: loud non-finite windows use the two stages
-    const int* rowPh;      // [Pc] polyphase phase / DFT parity of each composite row
-    const int* rowPar;
-    const double* polyA;   // [L][T2] polyphase bank a (polyphase_stage.go:121-154)
-    const double* dftC;    // [2][T1] DFT x2 banks (dft_stage.go:88-101)
-    int T1, T2;
+    ExactDev ex;           // HxDev::ex
 };
 
 // ---- staging ----------------------------------------------------------------
@@ -375,36 +366,7 @@ __device__ __forceinline__ bool hxBitsAny(const uint32_t* m, int lo, int hi) {
     return false;
 }
 
-// Exact value of output (a, r) of channel c in f64 from the stream itself:
-// the FIR row, or -- when the window holds Inf/NaN and the row is a DFT x2 (*)
-// polyphase composite -- the reference's two stages (a DFT output touched by
-// an Inf is +-Inf, their polyphase sum NaN; dft_stage.go:259, polyphase_stage.go:288).
-__device__ __forceinline__ double hxExact(HxArgsP x, int64_t a, int r, int c) {
-    const SrcDesc src = kload(&x->src);
-    const int64_t t = a * x->Qc + x->rowOff[r];
-    const int len = x->rowLen[r];
-    const double* row = x->rows + static_cast<size_t>(r) * x->rowMax;
-    double s = 0.0, z = 0.0;
-    for (int k = 0; k < len; ++k) {
-        const double v = static_cast<double>(srcRead<float>(src, t + k, c));  // history is f32
-        s += row[k] * v;
-        z += v * 0.0;
-    }
-    if (z == z || !x->twoStage) return s;  // finite window (or single-stage FIR: IEEE order-free)
-    const int ph = x->rowPh[r], par = x->rowPar[r], T1 = x->T1, T2 = x->T2;
-    const double* pa = x->polyA + static_cast<size_t>(ph) * T2;
-    double y = 0.0;
-    for (int k2 = 0; k2 < T2; ++k2) {
-        const int q = par + k2;
-        const double* cq = x->dftC + static_cast<size_t>(q & 1) * T1;
-        double u = 0.0;
-        for (int k1 = 0; k1 < T1; ++k1) u += cq[k1] * static_cast<double>(srcRead<float>(src, t + (q >> 1) + k1, c));
-        y += pa[k2] * u;
-    }
-    return y;
-}
-
-// Recompute, exactly, every output of block b whose window holds a loud
+// Recompute, exactly (gar_bg.hpp firExact), every output of block b whose window holds a loud
 // element (all threads of the workgroup; lmask = this buffer's column masks).
 __device__ __forceinline__ void hxFixupBlock(HxArgsP xp, int b, const uint32_t* lmask) {
     const HxArgs& x = *(const HxArgs*)(xp);
@@ -419,9 +381,9 @@ __device__ __forceinline__ void hxFixupBlock(HxArgsP xp, int b, const uint32_t* 
         const int64_t a = x.a_lo + static_cast<int64_t>(chunk) * x.G + gi;
         const int64_t o = a * x.Pc + r;
         if (o < x.o_lo || o >= x.o_hi) continue;
-        const int lo = gi * x.Qc + x.rowOff[r];
-        if (!hxBitsAny(lmask + n * wpc, lo, lo + x.rowLen[r])) continue;
-        outWrite<float>(x.od, o, c, static_cast<float>(hxExact(xp, a, r, c)));
+        const int lo = gi * x.Qc + x.ex.rowOff[r];
+        if (!hxBitsAny(lmask + n * wpc, lo, lo + x.ex.rowLen[r])) continue;
+        outWrite<float>(x.od, o, c, static_cast<float>(firExact<float>(&xp->ex, kload(&xp->src), xp->Qc, a, r, c).y));
     }
 }
 

@@ -179,17 +179,7 @@ HxsArgs hxsArgsOf(const HxsLaunchPlan& pl, const HxDev& p, const SrcDesc& src, c
     x.coop = std::max(0, std::min(2, k.coop));
     x.src = src;
     x.od = od;
-    x.rows = p.rows;
-    x.rowOff = p.rowOff;
-    x.rowLen = p.rowLen;
-    x.rowMax = p.rowMax;
-    x.twoStage = p.twoStage;
-    x.rowPh = p.rowPh;
-    x.rowPar = p.rowPar;
-    x.polyA = p.polyA;
-    x.dftC = p.dftC;
-    x.T1 = p.T1;
-    x.T2 = p.T2;
+    x.ex = p.ex;
     if (pl.qGroups > 0) {  // hxq_kernel takes each row-block program's first row / row block by value
         x.qOpt = pl.qOpt;
         x.qRbs = pl.qRbs;

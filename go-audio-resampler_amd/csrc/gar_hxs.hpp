@@ -22,8 +22,8 @@
 //    W/(G*Qc) = 1.34x; here (Np*Qc + Kread - Qc)/(Np*Qc) ~ 1.02x).
 //  * Loud elements (!(|x| < kHxLoud): |x| >= 16 - 2^-8, Inf, NaN) are staged as zero and their
 //    column-relative row range recorded; after the block, every output whose
-//    window holds one is recomputed exactly (hxExactT: f64, two stages when
-//    non-finite) by the same workgroup.
+//    window holds one is recomputed exactly (hxsFixup -> gar_bg.hpp firExact: f64, two stages
+//    when non-finite) by the same workgroup.
 #pragma once
 #include <climits>
 
@@ -72,19 +72,10 @@ struct HxsArgs {
     char* out;             // output (o, c) at out + o*out_fs + c*out_cs (bytes), o absolute
     int64_t out_fs, out_cs;
     int out_f64;
-    // cold fields: edge gathers and the exact fallback (hxExactT)
+    // cold fields: edge gathers and the exact fallback (hxsFixup)
     SrcDesc src;
     OutDesc od;
-    const double* rows;
-    const int* rowOff;
-    const int* rowLen;
-    int rowMax;
-    int twoStage;
-    const int* rowPh;
-    const int* rowPar;
-    const double* polyA;
-    const double* dftC;
-    int T1, T2;
+    ExactDev ex;           // HxDev::ex
     // hxt_kernel (gar_hxt.hpp): compute wave w runs row block role[w] & 0xff on the periods p with
     // p % stride == phase (phase = (role[w] >> 8) & 0xff, stride = role[w] >> 16)
     int ncomp;
@@ -132,32 +123,6 @@ __device__ __forceinline__ int hxsBlock(const HxsArgs& x, int i) {
     return ((s >> 1) * 8 + xc) * 2 + (s & 1);
 }
 
-// Exact value of output (a, r) of channel c (see hxExact in gar_hx.hpp).
-__device__ __forceinline__ double hxsExact(HxsArgsP x, int64_t a, int r, int c) {
-    const SrcDesc src = kload(&x->src);
-    const int64_t t = a * x->Qc + x->rowOff[r];
-    const int len = x->rowLen[r];
-    const double* row = x->rows + static_cast<size_t>(r) * x->rowMax;
-    double s = 0.0, z = 0.0;
-    for (int k = 0; k < len; ++k) {
-        const double v = static_cast<double>(srcRead<float>(src, t + k, c));
-        s += row[k] * v;
-        z += v * 0.0;
-    }
-    if (z == z || !x->twoStage) return s;
-    const int ph = x->rowPh[r], par = x->rowPar[r], T1 = x->T1, T2 = x->T2;
-    const double* pa = x->polyA + static_cast<size_t>(ph) * T2;
-    double y = 0.0;
-    for (int k2 = 0; k2 < T2; ++k2) {
-        const int q = par + k2;
-        const double* cq = x->dftC + static_cast<size_t>(q & 1) * T1;
-        double u = 0.0;
-        for (int k1 = 0; k1 < T1; ++k1) u += cq[k1] * static_cast<double>(srcRead<float>(src, t + (q >> 1) + k1, c));
-        y += pa[k2] * u;
-    }
-    return y;
-}
-
 // outWrite of the fixups; DITHER (the kernels of a launch with dither on, integer PCM output): the sample goes
 // through the dithered quantizer, at the position every other store of the launch gives it.
 template <bool DITHER>
@@ -171,33 +136,38 @@ __device__ __forceinline__ void hxsOutWrite(const OutDesc& od, int64_t o, int c,
     outWrite<float>(od, o, c, v);
 }
 
-// After a block: recompute every output whose window intersects a column's loud
-// row range and really holds a loud element (all threads; out of line).
+// After a block: recompute (gar_bg.hpp firExact) every output whose window intersects a column's loud
+// row range and really holds a loud element (all threads).  hxq_kernel restricts it to the output rows
+// [r0, r1) of each period, its workgroup's row blocks: another workgroup owns -- and stores -- the others.
 template <bool DITHER = false>
-__device__ __forceinline__ void hxsFixup(HxsArgsP xp, int b, const int* loudLo, const int* loudHi) {
+__device__ __forceinline__ void hxsFixup(HxsArgsP xp, int b, const int* loudLo, const int* loudHi, int r0 = 0,
+                                         int r1 = INT_MAX) {
     const SrcDesc src = kload(&xp->src);
     const OutDesc od = kload(&xp->od);
     const int Pc = xp->Pc, Qc = xp->Qc, Np = xp->Np, C = xp->C, ncols = xp->ncols;
+    const int nr = min(r1, Pc) - r0;
+    const bool ranged = r0 != 0 || r1 != INT_MAX;  // a constant where inlined; a ranged call may hold no row (nr <= 0)
     const int64_t a_lo = xp->a_lo, a_hi = xp->a_hi;
     for (int j = 0; j < 16; ++j) {
         const int lo = loudLo[j], hi = loudHi[j];
         const int col = b * 16 + j;
-        if (hi < 0 || col >= ncols) continue;
+        if (hi < 0 || col >= ncols || (ranged && nr <= 0)) continue;
         const int k = col / C, c = col - k * C;
         const int p0 = max(0, (lo - xp->Kread) / Qc), p1 = min(Np - 1, hi / Qc);
-        const int n = (p1 - p0 + 1) * Pc;
+        const int n = (p1 - p0 + 1) * nr;
         for (int idx = threadIdx.x; idx < n; idx += blockDim.x) {
-            const int p = p0 + idx / Pc, r = idx - (idx / Pc) * Pc;
+            const int p = p0 + idx / nr, r = r0 + (idx - (idx / nr) * nr);
             const int64_t a = a_lo + static_cast<int64_t>(k) * Np + p;
             if (a >= a_hi) continue;
             const int64_t o = a * Pc + r;
             if (o < od.o_lo || o >= od.o_hi) continue;
-            const int w0 = p * Qc + xp->rowOff[r], w1 = w0 + xp->rowLen[r];
+            const int w0 = p * Qc + xp->ex.rowOff[r], w1 = w0 + xp->ex.rowLen[r];
             if (w1 <= lo || w0 > hi) continue;
-            const int64_t t0 = a * Qc + xp->rowOff[r];
+            const int64_t t0 = a * Qc + xp->ex.rowOff[r];
             bool loud = false;
             for (int kk = 0; kk < w1 - w0 && !loud; ++kk) loud = hxLoud(srcRead<float>(src, t0 + kk, c));
-            if (loud) hxsOutWrite<DITHER>(od, o, c, static_cast<float>(hxsExact(xp, a, r, c)));
+            if (loud)
+                hxsOutWrite<DITHER>(od, o, c, static_cast<float>(firExact<float>(&xp->ex, kload(&xp->src), xp->Qc, a, r, c).y));
         }
     }
 }
@@ -1188,39 +1158,6 @@ __device__ __forceinline__ void hxqPut(char* ring, uint32_t QS, uint32_t Rt, int
     *reinterpret_cast<uint2*>(qb + 8 * Rt) = lv;
 }
 
-// hxsFixup restricted to output rows [r0, r1) of each period (the workgroup's row blocks: another
-// workgroup owns -- and stores -- the other rows).
-template <bool DITHER>
-__device__ __forceinline__ void hxqFixup(HxsArgsP xp, int b, const int* loudLo, const int* loudHi, int r0, int r1) {
-    const SrcDesc src = kload(&xp->src);
-    const OutDesc od = kload(&xp->od);
-    const int Qc = xp->Qc, Np = xp->Np, C = xp->C, ncols = xp->ncols, Pc = xp->Pc;
-    r1 = min(r1, Pc);
-    const int nr = r1 - r0;
-    const int64_t a_lo = xp->a_lo, a_hi = xp->a_hi;
-    for (int j = 0; j < 16; ++j) {
-        const int lo = loudLo[j], hi = loudHi[j];
-        const int col = b * 16 + j;
-        if (hi < 0 || col >= ncols || nr <= 0) continue;
-        const int k = col / C, c = col - k * C;
-        const int p0 = max(0, (lo - xp->Kread) / Qc), p1 = min(Np - 1, hi / Qc);
-        const int n = (p1 - p0 + 1) * nr;
-        for (int idx = threadIdx.x; idx < n; idx += blockDim.x) {
-            const int p = p0 + idx / nr, r = r0 + (idx - (idx / nr) * nr);
-            const int64_t a = a_lo + static_cast<int64_t>(k) * Np + p;
-            if (a >= a_hi) continue;
-            const int64_t o = a * Pc + r;
-            if (o < od.o_lo || o >= od.o_hi) continue;
-            const int w0 = p * Qc + xp->rowOff[r], w1 = w0 + xp->rowLen[r];
-            if (w1 <= lo || w0 > hi) continue;
-            const int64_t t0 = a * Qc + xp->rowOff[r];
-            bool loud = false;
-            for (int kk = 0; kk < w1 - w0 && !loud; ++kk) loud = hxLoud(srcRead<float>(src, t0 + kk, c));
-            if (loud) hxsOutWrite<DITHER>(od, o, c, static_cast<float>(hxsExact(xp, a, r, c)));
-        }
-    }
-}
-
 template <int NS, int VST, bool DITHER = false>
 __global__ __launch_bounds__(64 * kHxqMaxWaves) void hxq_kernel(HxsArgs x) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1441,7 +1378,7 @@ __global__ __launch_bounds__(64 * kHxqMaxWaves) void hxq_kernel(HxsArgs x) {
     if (*flag) {  // uniform (LDS after the barrier)
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
-        hxqFixup<DITHER>(hxsCold(), b, loudLo, loudHi, 16 * r0, 16 * (r0 + nrw));
+        hxsFixup<DITHER>(hxsCold(), b, loudLo, loudHi, 16 * r0, 16 * (r0 + nrw));
     }
     const unsigned long long tOut = (kHxsDev && x.prof) ? __builtin_amdgcn_s_memtime() : 0;
     if (x.hn > 0) {

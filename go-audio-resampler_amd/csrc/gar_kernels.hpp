@@ -194,6 +194,21 @@ constexpr int kHxtErrLoadWait = 1, kHxtErrSlotWait = 2;
 std::string& launchLimitMsg();
 hipError_t ldsTooBig(const char* kernel, size_t need, size_t limit);
 
+// Device copy of a plan's ExactRows (gar_plan.hpp; uploaded by gar_stage.cpp uploadExact), read by the one
+// exact recompute, firExact (gar_bg.hpp).  A launch's argument block embeds it as it is.
+struct ExactDev {
+    const double* rows;   // [Pc][rowMax] FIR rows (f64)
+    const int* rowOff;    // [Pc] window offset of row r within its macro period
+    const int* rowLen;    // [Pc]
+    int rowMax;
+    int twoStage;         // rows are DFT x2 (*) polyphase composites: a non-finite window runs the two stages
+    const int* rowPh;     // [Pc] polyphase phase of each composite row
+    const int* rowPar;    // [Pc] DFT output parity of each composite row
+    const double* polyA;  // [L][T2] polyphase bank a (polyphase_stage.go:121-154), one upload per stage
+    const double* dftC;   // [2][T1] DFT x2 banks (dft_stage.go:88-101), one upload per stage
+    int T1, T2;           // DFT taps per phase, polyphase taps per phase
+};
+
 // Device copy of a BgPlan (gar_plan.hpp).
 struct BgDev {
     int f64;
@@ -208,37 +223,21 @@ struct BgDev {
     const int* rbStart; // [nrb + 1]
     const int* hRbStart; // host copies (bg_rb_kernel passes them by value): [nrb + 1]
     const int* hRbK0;    // first input row of each program [nprog]
-    // exact recompute of outputs whose real window holds a non-finite sample (gar_bg.hpp bgNfFixOne):
-    // the macro period's f64 rows and, for DFT x2 (*) polyphase composites, each row's polyphase
-    // phase / DFT parity and the two stages' banks (the reference's two-stage order)
-    const double* xRows;   // [Pc][xRowMax]
-    const int* xInfo;      // [4][Pc]: window offset, length, polyphase phase, DFT parity
-    int xRowMax, xTwoStage, xT1, xT2;
-    const double* xPolyA;  // [L][T2]
-    const double* xDftC;   // [2][T1]
-    int* nfList;           // bg_kernel's non-finite fix list (gar_bg.hpp kBgNfInts ints, zeroed)
+    ExactDev ex;           // outputs whose real window holds a non-finite sample (gar_bg.hpp bgNfFixOne)
+    int* nfList;          // bg_kernel's non-finite fix list (gar_bg.hpp kBgNfInts ints, zeroed)
 };
 constexpr size_t kBgNfListBytes = 4 * (2 + 256 * 129 + 1);  // gar_bg.hpp kBgNfInts (static_assert there)
 
 // Device copy of an HxPlan (gar_plan.hpp): split-f16 MFMA FIR, f32 compute.
 struct HxDev {
     int Pc, Qc, Kc, Kread, NS, nrb;
-    int nw, kch, nred, nslots, ea, rowMax;
+    int nw, kch, nred, nslots, ea;
     int rb;              // row-block mode (HxPlan::rbMode)
     const void* A;       // [nw][kch*NS][2][64][8] f16
     const int* progs;    // [nw][kBgProgInts] (HxPlan::progTable)
     const int* reds;     // [nred][kBgRedInts]
-    // exact fallback of outputs whose windows hold a loud element: !(|x| < kHxLoud = 16 - 2^-8), Inf, NaN
-    const double* rows;  // [Pc][rowMax] FIR rows (f64)
-    const int* rowOff;   // [Pc]
-    const int* rowLen;   // [Pc]
-    int twoStage;        // rows are DFT x2 (*) polyphase composites (HxPlan::twoStage)
-    int T1, T2;          // DFT taps per phase, polyphase taps per phase
-    const int* rowPh;    // [Pc] polyphase phase of each composite row
-    const int* rowPar;   // [Pc] DFT output parity of each composite row
-    const double* polyA; // [L][T2]
-    const double* dftC;  // [2][T1]
-    int* fix;            // [1 + fixCap]: interior blocks holding loud elements (count first)
+    ExactDev ex;         // outputs whose windows hold a loud element: !(|x| < kHxLoud = 16 - 2^-8), Inf, NaN
+    int* fix;           // [1 + fixCap]: interior blocks holding loud elements (count first)
     int fixCap;
     int hxsOk;           // host: the plan fits hxs_kernel (hxsPlanFits), so fused PCM I/O can use it
     int hU0[16], hRbw[16];  // host copies of each row-block program's first row / row block (rb mode, nw <= 16)

@@ -117,6 +117,31 @@ std::vector<RbGeom> geomFor(const FirPeriodic& f, int mp, double& eff, int kstep
 }
 }  // namespace
 
+ExactRows buildExactRows(const FirPeriodic& f, int mp) {
+    ExactRows x;
+    const int Pc = f.P * mp;
+    for (const auto& r : f.rows) x.rowMax = std::max(x.rowMax, static_cast<int>(r.size()));
+    x.twoStage = f.composite;
+    x.rows.assign(static_cast<size_t>(Pc) * x.rowMax, 0.0);
+    x.off.assign(Pc, 0);
+    x.len.assign(Pc, 0);
+    x.ph.assign(Pc, 0);
+    x.par.assign(Pc, 0);
+    for (int r = 0; r < Pc; ++r) {
+        int64_t off;
+        const std::vector<double>* row;
+        macroRow(f, r, off, row);
+        x.off[r] = static_cast<int>(off);
+        x.len[r] = static_cast<int>(row->size());
+        if (f.composite) {
+            x.ph[r] = f.ph[r % f.P];
+            x.par[r] = f.par[r % f.P];
+        }
+        std::copy(row->begin(), row->end(), x.rows.begin() + static_cast<size_t>(r) * x.rowMax);
+    }
+    return x;
+}
+
 namespace {
 // Even split of the row blocks' steps over nprog programs (<= kBgMaxSeg
 // segments each); row blocks cut across programs get LDS slots + a reduction.
@@ -347,23 +372,7 @@ bool buildBgPlan(const FirPeriodic& f, bool f64, BgPlan& plan) {
     if (f64) plan.A64 = std::move(A);
     else plan.A32.assign(A.begin(), A.end());
 
-    plan.rowMax = 0;
-    for (const auto& r : f.rows) plan.rowMax = std::max(plan.rowMax, static_cast<int>(r.size()));
-    plan.twoStage = f.composite;
-    plan.rows.assign(static_cast<size_t>(plan.Pc) * plan.rowMax, 0.0);
-    plan.rowInfo.assign(4 * static_cast<size_t>(plan.Pc), 0);
-    for (int r = 0; r < plan.Pc; ++r) {
-        int64_t off;
-        const std::vector<double>* row;
-        macroRow(f, r, off, row);
-        plan.rowInfo[r] = static_cast<int>(off);
-        plan.rowInfo[plan.Pc + r] = static_cast<int>(row->size());
-        if (f.composite) {
-            plan.rowInfo[2 * plan.Pc + r] = f.ph[r % f.P];
-            plan.rowInfo[3 * plan.Pc + r] = f.par[r % f.P];
-        }
-        std::copy(row->begin(), row->end(), plan.rows.begin() + static_cast<size_t>(r) * plan.rowMax);
-    }
+    plan.ex = buildExactRows(f, plan.mp);
 
     double useful = 0;
     for (const auto& r : f.rows) useful += static_cast<double>(r.size());
@@ -515,26 +524,7 @@ bool buildHxPlan(const FirPeriodic& f, HxPlan& plan) {
         }
     }
 
-    plan.rowMax = 0;
-    for (const auto& r : f.rows) plan.rowMax = std::max(plan.rowMax, static_cast<int>(r.size()));
-    plan.rows.assign(static_cast<size_t>(plan.Pc) * plan.rowMax, 0.0);
-    plan.rowOff.assign(plan.Pc, 0);
-    plan.rowLen.assign(plan.Pc, 0);
-    plan.twoStage = f.composite;
-    plan.rowPh.assign(plan.Pc, 0);
-    plan.rowPar.assign(plan.Pc, 0);
-    for (int r = 0; r < plan.Pc; ++r) {
-        int64_t off;
-        const std::vector<double>* row;
-        macroRow(f, r, off, row);
-        plan.rowOff[r] = static_cast<int>(off);
-        plan.rowLen[r] = static_cast<int>(row->size());
-        for (size_t k = 0; k < row->size(); ++k) plan.rows[static_cast<size_t>(r) * plan.rowMax + k] = (*row)[k];
-        if (f.composite) {
-            plan.rowPh[r] = f.ph[r % f.P];
-            plan.rowPar[r] = f.par[r % f.P];
-        }
-    }
+    plan.ex = buildExactRows(f, plan.mp);
 
     double useful = 0;
     for (const auto& r : f.rows) useful += static_cast<double>(r.size());

@@ -38,6 +38,18 @@ FirPeriodic firFromDecim(const DecimBank& d);
 bool firFromPoly(const PolyBank& p, FirPeriodic& out);                          // needs fracFree()
 bool firComposite(const DftBank& d, const PolyBank& p, FirPeriodic& out);       // needs factor 2 + fracFree()
 
+// Exact rows of a plan's macro period (Pc = mp * P outputs): what the exact recompute of an output
+// from the stream itself reads (gar_bg.hpp firExact; uploaded as an ExactDev, gar_kernels.hpp).
+// Every x == 0 kernel family falls back to it for the outputs whose real window holds a sample its
+// MFMA path cannot carry.  ph / par: polyphase phase / DFT output parity of a composite's rows.
+struct ExactRows {
+    int rowMax = 0;
+    bool twoStage = false;               // rows are DFT x2 (*) polyphase composites (FirPeriodic::composite)
+    std::vector<double> rows;            // [Pc][rowMax] f64, zero padded
+    std::vector<int> off, len, ph, par;  // [Pc] each: window offset within the macro period, length, phase, parity
+};
+ExactRows buildExactRows(const FirPeriodic& f, int mp);
+
 // Wave program = the MFMA steps one wavefront runs per macro period: up to 3
 // segments, each a contiguous K range of one row block.  The total step count
 // of all row blocks is split evenly over the programs so every SIMD carries
@@ -83,12 +95,7 @@ struct BgPlan {
     std::vector<int> rbK0;            // first input row of each program (one segment each)
     std::vector<float> A32;           // [nw][kch*NS][64] MFMA A fragments
     std::vector<double> A64;
-    // exact rows of the macro period (non-finite fixup, BgDev::xRows): f64 rows [Pc][rowMax] and
-    // [offset | length | polyphase phase | DFT parity] per row (phase / parity of composite rows)
-    int rowMax = 0;
-    bool twoStage = false;
-    std::vector<double> rows;
-    std::vector<int> rowInfo;
+    ExactRows ex;                     // exact recompute of outputs whose real window is non-finite
     double usefulMacsPerOutput = 0;   // sum of row lengths / P
     double mfmaMacsPerOutput = 0;     // MFMA MACs / output over the band (excl. bucket padding)
     std::vector<int> progTable() const;  // [nprog][kBgProgInts]
@@ -136,11 +143,7 @@ struct HxPlan {
     std::vector<BgProg> progs;        // [nw]; BgSeg::k0 = first input row of the segment
     std::vector<BgRed> reds;
     std::vector<uint16_t> A;          // [nw][kch*NS][2 (hi, lo)][64 lanes][8] f16 bits
-    int rowMax = 0;                   // exact fallback (loud windows): f64 rows [Pc][rowMax], offsets, lengths
-    std::vector<double> rows;
-    std::vector<int> rowOff, rowLen;
-    bool twoStage = false;            // composite rows: per-row polyphase phase / DFT parity
-    std::vector<int> rowPh, rowPar;
+    ExactRows ex;                     // exact recompute of outputs whose window holds a loud element
     double usefulMacsPerOutput = 0;
     double mfmaMacsPerOutput = 0;     // executed MACs (one of the three products) per output
     std::vector<int> progTable() const;  // [nw][kBgProgInts]

@@ -7,10 +7,38 @@
 namespace gar {
 namespace {
 
-// Builds + uploads the split-f16 plan of `f` and points bg.hx at it; `ed` (the
-// engine design) supplies the two stages of a composite FIR for the exact
-// fallback of non-finite windows.
-bool attachHx(const FirPeriodic& f, StageRT::HxRT& h, BgDev& bg, bool dry, const EngineDesign& ed) {
+// The exact rows of a plan as the device sees them: [rows (f64) | off | len | ph | par] in X; the two
+// stages' banks of a composite are uploaded once per stage (xBankA / xBankC) and shared by its plans.
+// A dry-run handle uploads nothing and gets the host-side scalars.
+ExactDev uploadExact(const ExactRows& x, StageRT& s, DevBuf& X, bool dry) {
+    ExactDev d{};
+    d.rowMax = x.rowMax;
+    d.twoStage = x.twoStage ? 1 : 0;
+    d.T1 = s.d.dft.taps;
+    d.T2 = s.d.poly.taps;
+    if (dry) return d;
+    const size_t nr = x.rows.size(), Pc = x.off.size();
+    std::vector<int> info = x.off;
+    for (const std::vector<int>* v : {&x.len, &x.ph, &x.par}) info.insert(info.end(), v->begin(), v->end());
+    X.ensure(nr * 8 + info.size() * 4);
+    HIPCHK(hipMemcpy(X.p, x.rows.data(), nr * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(static_cast<char*>(X.p) + nr * 8, info.data(), info.size() * 4, hipMemcpyHostToDevice));
+    d.rows = static_cast<const double*>(X.p);
+    d.rowOff = reinterpret_cast<const int*>(d.rows + nr);
+    d.rowLen = d.rowOff + Pc;
+    d.rowPh = d.rowOff + 2 * Pc;
+    d.rowPar = d.rowOff + 3 * Pc;
+    if (x.twoStage) {
+        if (!s.xBankA.p) s.xBankA.upload(s.d.poly.a);
+        if (!s.xBankC.p) s.xBankC.upload(s.d.dft.c);
+        d.polyA = static_cast<const double*>(s.xBankA.p);
+        d.dftC = static_cast<const double*>(s.xBankC.p);
+    }
+    return d;
+}
+
+// Builds + uploads the split-f16 plan of `f` and points bg.hx at it.
+bool attachHx(const FirPeriodic& f, StageRT::HxRT& h, BgDev& bg, bool dry, StageRT& s) {
     if (!buildHxPlan(f, h.plan)) return false;
     HxDev& d = h.d;
     const HxPlan& p = h.plan;
@@ -22,10 +50,8 @@ bool attachHx(const FirPeriodic& f, StageRT::HxRT& h, BgDev& bg, bool dry, const
     d = HxDev{};
     d.Pc = p.Pc; d.Qc = p.Qc; d.Kc = p.Kc; d.Kread = p.Kread; d.NS = p.NS; d.nrb = p.nrb;
     d.nw = p.nw; d.kch = p.kch; d.nred = static_cast<int>(p.reds.size()); d.nslots = p.nslots;
-    d.ea = p.ea; d.rowMax = p.rowMax; d.rb = p.rbMode ? 1 : 0;
-    d.twoStage = p.twoStage ? 1 : 0;
-    d.T1 = ed.dft.taps;
-    d.T2 = ed.poly.taps;
+    d.ea = p.ea; d.rb = p.rbMode ? 1 : 0;
+    d.ex = uploadExact(p.ex, s, h.X, dry);
     if (p.rbMode && p.nw <= 16) {  // hxq_kernel takes them by value
         const std::vector<int> pt = p.progTable();
         for (int w = 0; w < p.nw; ++w) { d.hU0[w] = pt[kBgProgInts * w + 4]; d.hRbw[w] = pt[kBgProgInts * w + 3]; }
@@ -37,29 +63,12 @@ bool attachHx(const FirPeriodic& f, StageRT::HxRT& h, BgDev& bg, bool dry, const
         const size_t redOff = t.size();
         t.insert(t.end(), rt.begin(), rt.end());
         h.T.upload(t);
-        h.rows.upload(p.rows);
-        std::vector<int> ri = p.rowOff;  // [rowOff | rowLen | rowPh | rowPar]
-        ri.insert(ri.end(), p.rowLen.begin(), p.rowLen.end());
-        ri.insert(ri.end(), p.rowPh.begin(), p.rowPh.end());
-        ri.insert(ri.end(), p.rowPar.begin(), p.rowPar.end());
-        h.rowInfo.upload(ri);
         d.A = h.A.p;
         d.progs = static_cast<const int*>(h.T.p);
         d.reds = static_cast<const int*>(h.T.p) + redOff;
-        d.rows = static_cast<const double*>(h.rows.p);
-        d.rowOff = static_cast<const int*>(h.rowInfo.p);
-        d.rowLen = d.rowOff + p.Pc;
-        d.rowPh = d.rowOff + 2 * p.Pc;
-        d.rowPar = d.rowOff + 3 * p.Pc;
         d.fixCap = 1 << 16;
         h.fix.upload(std::vector<int>(1 + d.fixCap, 0));
         d.fix = static_cast<int*>(h.fix.p);
-        if (p.twoStage) {
-            h.banks.upload(ed.poly.a);
-            h.banks2.upload(ed.dft.c);
-            d.polyA = static_cast<const double*>(h.banks.p);
-            d.dftC = static_cast<const double*>(h.banks2.p);
-        }
     }
     d.hxsOk = hxsPlanFits(d) ? 1 : 0;  // PCM / half stores and loads fuse only into hxs_kernel (pcmFusable)
     bg.hx = &h.d;
@@ -97,30 +106,13 @@ BgDev uploadPlan(const BgPlan& p, DevBuf& A, DevBuf& T, bool dry) {
     return d;
 }
 
-// Exact rows of a plan (non-finite fixup, BgDev::xRows): [rows | rowInfo] in one buffer; the
-// composite's two stages' banks are shared by the stage (xBankA / xBankC).
-void attachExact(const BgPlan& p, DevBuf& X, StageRT& s, BgDev& d, bool dry) {
-    d.xRowMax = p.rowMax;
-    d.xTwoStage = p.twoStage ? 1 : 0;
-    d.xT1 = s.d.dft.taps;
-    d.xT2 = s.d.poly.taps;
+// A bg plan's exact rows and bg_kernel's non-finite fix list (kBgNfInts ints, zeroed).
+void attachExact(const BgPlan& p, StageRT::BgX& x, StageRT& s, BgDev& d, bool dry) {
+    d.ex = uploadExact(p.ex, s, x.rows, dry);
     if (dry) return;
-    // [rows (f64) | rowInfo (int) | bg_kernel's fix list (kBgNfInts ints, zeroed)]
-    const size_t nr = p.rows.size(), ni = p.rowInfo.size();
-    const size_t listOff = (nr * 8 + ni * 4 + 15) / 16 * 16;
-    X.ensure(listOff + kBgNfListBytes);
-    HIPCHK(hipMemcpy(X.p, p.rows.data(), nr * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(static_cast<char*>(X.p) + nr * 8, p.rowInfo.data(), ni * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(static_cast<char*>(X.p) + listOff, 0, kBgNfListBytes));
-    d.xRows = static_cast<const double*>(X.p);
-    d.xInfo = reinterpret_cast<const int*>(static_cast<const char*>(X.p) + nr * 8);
-    d.nfList = reinterpret_cast<int*>(static_cast<char*>(X.p) + listOff);
-    if (p.twoStage) {
-        if (!s.xBankA.p) s.xBankA.upload(s.d.poly.a);
-        if (!s.xBankC.p) s.xBankC.upload(s.d.dft.c);
-        d.xPolyA = static_cast<const double*>(s.xBankA.p);
-        d.xDftC = static_cast<const double*>(s.xBankC.p);
-    }
+    x.nfList.ensure(kBgNfListBytes);
+    HIPCHK(hipMemset(x.nfList.p, 0, kBgNfListBytes));
+    d.nfList = static_cast<int*>(x.nfList.p);
 }
 
 template <class T>
@@ -140,20 +132,20 @@ bool buildStage(StageRT& s, bool f64, bool hx, bool dry, std::string& err) {
         if (!buildBgPlan(firFromDft(d.dft), f64, s.dftP)) { err = "DFT plan"; return false; }
         s.dftD = uploadPlan(s.dftP, s.dftA, s.dftT, dry);
         attachExact(s.dftP, s.dftX, s, s.dftD, dry);
-        if (hx) attachHx(firFromDft(d.dft), s.dftH, s.dftD, dry, d);
+        if (hx) attachHx(firFromDft(d.dft), s.dftH, s.dftD, dry, s);
     }
     if (d.kind == EngineKind::Decim) {
         if (!buildBgPlan(firFromDecim(d.decim), f64, s.decimP)) { err = "decimator plan"; return false; }
         s.decimD = uploadPlan(s.decimP, s.decimA, s.decimT, dry);
         attachExact(s.decimP, s.decimX, s, s.decimD, dry);
-        if (hx) attachHx(firFromDecim(d.decim), s.decimH, s.decimD, dry, d);
+        if (hx) attachHx(firFromDecim(d.decim), s.decimH, s.decimD, dry, s);
     }
     if (d.kind == EngineKind::DftPoly) {
         if (firComposite(d.dft, d.poly, s.compositeFir) && buildBgPlan(s.compositeFir, f64, s.fusedP)) {
             s.fused = true;
             s.fusedD = uploadPlan(s.fusedP, s.fusedA, s.fusedT, dry);
             attachExact(s.fusedP, s.fusedX, s, s.fusedD, dry);
-            if (hx) attachHx(s.compositeFir, s.fusedH, s.fusedD, dry, d);
+            if (hx) attachHx(s.compositeFir, s.fusedH, s.fusedD, dry, s);
         }
         PolyDev& p = s.polyD;
         p.f64 = s.cf();

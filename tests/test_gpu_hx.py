@@ -223,6 +223,84 @@ def test_hx_values_just_below_16(gar, O, cuda, chunks):
         np.testing.assert_array_equal(got, one)
 
 
+_HX_CHILD = """
+import sys
+import numpy as np
+import torch
+sys.path.insert(0, sys.argv[1])
+import gar
+ir, orr, src, dst = int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], sys.argv[5]
+x = torch.from_numpy(np.load(src)).cuda()
+def run(ck):
+    r = gar.New(gar.Config(ir, orr, x.shape[1], gar.QualityHigh, ComputeDtype=gar.F32))
+    parts = [r.process_device(x[s:s + ck]).clone() for s in range(0, x.shape[0], ck)]
+    parts.append(r.flush_device(dtype=torch.float32).clone())
+    torch.cuda.synchronize()
+    return torch.cat(parts).cpu().numpy()
+np.savez(dst, one=run(x.shape[0]), chunked=run(997))
+"""
+
+
+def _hazard_input(rate):
+    """12,000 stereo frames with one loud run (40 samples x 1000) and a +Inf, a NaN and a -Inf 2,500 frames apart."""
+    x = signal(12000, 2, rate, seed=31).astype(np.float32).astype(np.float64)
+    x[1500:1540, 0] *= 1000.0
+    x[4000, 1] = np.inf
+    x[6500, 0] = np.nan
+    x[9000, 1] = -np.inf
+    return x.astype(np.float32)
+
+
+@pytest.mark.parametrize("ir,orr,hxs_off", [(44100, 48000, True), (88200, 44100, False)])
+def test_hx_kernel_exact_fallback(O, cuda, tmp_path, ir, orr, hxs_off):
+    """hx_kernel's exact recompute of loud and non-finite windows (hxFixupBlock -> firExact), which no other GPU test
+    reaches for a composite: a row-block plan streams through hxs / hxq / hxt unless GAR_HXS=0, and that knob is read
+    once per process, so a fresh child runs the stream (GAR_HX_TRACE=1: its launches are `hx:` lines).
+    44.1k -> 48k High with GAR_HXS=0 is a DFT x2 (*) polyphase composite -- the non-finite windows take the two-stage
+    half; 88.2k -> 44.1k High is an integer decimator whose split-f16 plan is segmented, hx_kernel by the default
+    route (the launch-plan cases' 88cd) -- the single-stage half.  One-shot and in 997-frame calls: every output's
+    NaN / +Inf / -Inf class is the oracle's, the finite ones are within the float32 bar, and the two runs are bit-equal.
+    The bar leaves room on this input: the loud run's ~45 (~20) outputs reach |y| ~ 900 (ulp 6e-5), so the oracle's own
+    values rounded to float32 are already 7.0e-7 (4.4e-7) RMS from it over the ~13,000 (6,000) outputs of channel 0 --
+    asserted to be within 0.75 of the bar; the split-f16 arithmetic of the other outputs (~1e-7) adds in quadrature.
+    The oracle alone leaves 96 % (85 %: the decimator's longer rows) of the Inf channel's outputs finite."""
+    import os
+    import subprocess
+    import sys
+    x = _hazard_input(ir)
+    want = oracle_new(O, ir, orr, x.astype(np.float64), O.P_HIGH)
+    src, dst = str(tmp_path / "x.npy"), str(tmp_path / "y.npz")
+    np.save(src, x)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, GAR_HX_TRACE="1")
+    if hxs_off:
+        env["GAR_HXS"] = "0"
+    p = subprocess.run([sys.executable, "-c", _HX_CHILD, os.path.join(root, "go-audio-resampler_amd"), str(ir), str(orr), src, dst],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stderr.splitlines() if ln.startswith(("hx:", "hxs:", "hxt:", "hxq:"))]
+    assert any(ln.startswith("hx:") for ln in lines), p.stderr[-2000:]
+    assert all(ln.startswith("hx:") for ln in lines), lines[:8]
+    y = np.load(dst)
+    one, chunked = y["one"], y["chunked"]
+    assert one.dtype == np.float32 and one.shape == chunked.shape
+    np.testing.assert_array_equal(one.view(np.uint32), chunked.view(np.uint32))
+    for c in range(2):
+        w = np.asarray(want[c])
+        fin = np.isfinite(w)
+        assert one.shape[0] == len(w)
+        # neither all finite nor mostly non-finite
+        assert (0.9 if hxs_off else 0.8) * len(w) < fin.sum() < len(w), (c, int(fin.sum()), len(w))
+        assert rms(w[fin].astype(np.float32), w[fin]) <= 0.75 * F32_RMS_TOL
+        g = one[:, c].astype(np.float64)
+        np.testing.assert_array_equal(np.isnan(g), np.isnan(w))
+        np.testing.assert_array_equal(np.isposinf(g), np.isposinf(w))
+        np.testing.assert_array_equal(np.isneginf(g), np.isneginf(w))
+        e = rms(g[fin], w[fin])
+        print("hx_kernel exact fallback %d -> %d ch%d: rms %.3e over %d finite of %d" % (ir, orr, c, e, fin.sum(), len(w)))
+        assert e <= F32_RMS_TOL, (c, e)
+
+
 def test_hxt_expired_wait_is_a_device_error(gar, cuda, monkeypatch):
     """An expired progress wait of the streaming kernel (hxt_kernel) is an error, not output
     (VERDICT r04 item 2): the development knob GAR_HXT_FAULT=1 makes the compute waves' load count

@@ -505,10 +505,21 @@ gar_status deviceCall(Handle* r, const DevIo* in, int64_t frames, const DevIo& o
         gar_status st;
         const int64_t got = runGroup(r, r->groups[0], iv, ov, flush, s, out_cap, st);
         if (st == GAR_OK && stageOut && got > 0)
-            HIPCHK(launchConvert(r->outStage.p, r->cf(), C, 1, out.p, out.dtype, out.fs, out.cs, got, C, s, dz));
+            HIPCHK(launchConvert(r->outStage.p, r->cf(), C, 1, out.p, out.dtype, out.fs, out.cs, got, C, s, dz,
+                                 (r->meterOn && isPcm(out.dtype)) ? static_cast<uint64_t*>(r->meterBuf.p) : nullptr));
         if (st == GAR_OK && out_frames) *out_frames = got;
         return st;
     });
+}
+
+// Zeroes the tallies of channels [ch0, ch0 + n) after the handle's enqueued work (gar_synchronize's wait), on the
+// handle's own stream, and returns once that stream has done it: ordered before any later call whichever stream it
+// uses, without a wait for anything else on the device.  Throws DevError.
+void meterZero(Handle* h, int32_t ch0, int32_t n) {
+    if (h->dry || !h->meterBuf.p || n <= 0) return;
+    waitEnqueued(h);
+    HIPCHK(hipMemsetAsync(static_cast<char*>(h->meterBuf.p) + 16 * static_cast<size_t>(ch0), 0, 16 * static_cast<size_t>(n), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
 }
 
 gar_status channelMismatch(const Handle* h, int32_t got) {
@@ -705,6 +716,12 @@ void gar_reset(gar_resampler* r) {
     if (!r) return;
     DeviceGuard dg(r->dry ? -1 : r->device);
     try {
+        if (r->meterBuf.p && !r->poisoned) meterZero(r, 0, r->channels);  // the tallies describe what was stored since the last reset
+    } catch (...) {
+        // a device error here poisons nothing by itself: the next call meets it and the recovery path below, which
+        // zeroes the tallies again once everything has drained
+    }
+    try {
         if (!r->dry) (void)devFault(r);  // a raised status word takes the recovery path (and is cleared there)
         if (r->poisoned) {  // recover: drain the handle's streams, fresh state
             // the failing call recorded no order event, and launches it already queued on its
@@ -719,6 +736,10 @@ void gar_reset(gar_resampler* r) {
             if (r->errHost) __atomic_store_n(r->errHost, 0, __ATOMIC_RELEASE);  // every launch that could write it has drained
             r->groups.clear();
             r->groups.push_back(freshGroup(r, 0, r->channels));
+            if (r->meterBuf.p && r->stream) {  // everything has drained; done before the next call on any stream
+                (void)hipMemsetAsync(r->meterBuf.p, 0, 16 * static_cast<size_t>(r->channels), r->stream);
+                (void)hipStreamSynchronize(r->stream);
+            }
             r->poisoned = false;
             r->failEvValid = false;
             r->orderValid = false;
@@ -852,6 +873,73 @@ gar_status gar_set_dither(gar_resampler* r, int32_t mode, uint64_t seed) {
     static_assert(kDitherNone == GAR_DITHER_NONE && kDitherTpdf == GAR_DITHER_TPDF, "the kernels' dither modes are the ABI's");
     r->ditherMode = mode;
     r->ditherSeed = seed;
+    return GAR_OK;
+}
+
+gar_status gar_set_meter(gar_resampler* r, int32_t on) {
+    if (!r) return guard(GAR_ERR_INVALID_ARGUMENT, "nil resampler");
+    if (on != 0 && on != 1) return guard(GAR_ERR_INVALID_ARGUMENT, "meter setting must be 0 or 1");
+    if (on && !r->dry && !r->meterBuf.p) {  // [channels] x {clips, peak bits}, zeroed
+        DeviceGuard dg(r->device);
+        const gar_status st = wrap([&]() -> gar_status {
+            r->meterBuf.ensure(16 * static_cast<size_t>(r->channels));
+            HIPCHK(hipMemsetAsync(r->meterBuf.p, 0, 16 * static_cast<size_t>(r->channels), r->stream));
+            HIPCHK(hipStreamSynchronize(r->stream));
+            return GAR_OK;
+        });
+        if (st != GAR_OK) {
+            r->meterBuf.release();
+            return st;
+        }
+    }
+    r->meterOn = on != 0;
+    return GAR_OK;
+}
+
+gar_status gar_get_meter(const gar_resampler* r, int32_t* on) {
+    if (!r) return guard(GAR_ERR_INVALID_ARGUMENT, "nil resampler");
+    if (on) *on = r->meterOn ? 1 : 0;
+    return GAR_OK;
+}
+
+gar_status gar_meter_read(gar_resampler* r, int32_t ch0, int32_t n_ch, uint64_t* clips, double* peak, int32_t reset) {
+    if (!r) return guard(GAR_ERR_INVALID_ARGUMENT, "nil resampler");
+    if (ch0 < 0 || n_ch < 0 || static_cast<int64_t>(ch0) + n_ch > r->channels)
+        return guard(GAR_ERR_INVALID_ARGUMENT, "meter channel range outside the handle");
+    const gar_status sy = gar_synchronize(r);  // the handle's enqueued calls; a raised status word: GAR_ERR_DEVICE
+    if (sy != GAR_OK) return sy;
+    std::vector<uint64_t> w(2 * static_cast<size_t>(n_ch), 0);
+    if (!r->dry && r->meterBuf.p && n_ch > 0) {
+        DeviceGuard dg(r->device);
+        const gar_status st = wrap([&]() -> gar_status {
+            HIPCHK(hipMemcpy(w.data(), static_cast<const char*>(r->meterBuf.p) + 16 * static_cast<size_t>(ch0), 16 * static_cast<size_t>(n_ch),
+                             hipMemcpyDeviceToHost));
+            if (reset) meterZero(r, ch0, n_ch);
+            return GAR_OK;
+        });
+        if (st != GAR_OK) return st;
+    }
+    for (int32_t i = 0; i < n_ch; ++i) {
+        if (clips) clips[i] = w[2 * i];
+        if (peak) peak[i] = __builtin_bit_cast(double, w[2 * i + 1]);
+    }
+    return GAR_OK;
+}
+
+gar_status gar_dev_meter_tally(int32_t pcm_type, int32_t dither_mode, uint64_t seed, int32_t channel, int64_t position0,
+                               const double* in, int64_t n, uint64_t* clips, double* peak) {
+    if (!isPcm(pcm_type) || (dither_mode != GAR_DITHER_NONE && dither_mode != GAR_DITHER_TPDF) || n < 0 || (n > 0 && !in) || channel < 0)
+        return guard(GAR_ERR_INVALID_ARGUMENT, "bad meter tally arguments");
+    uint64_t total = 0, pk = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t c = 0;
+        // what the kernels tally (meterTallyAt: the checked stores and the staged kernels call it as is)
+        meterTallyAt(in[i], pcm_type, dither_mode, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32),
+                     static_cast<uint32_t>(channel), static_cast<uint64_t>(position0) + static_cast<uint64_t>(i), c, pk);
+        total += c;
+    }
+    if (clips) *clips = total;
+    if (peak) *peak = __builtin_bit_cast(double, pk);
     return GAR_OK;
 }
 

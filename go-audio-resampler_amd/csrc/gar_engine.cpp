@@ -63,7 +63,9 @@ hipError_t timed(Ctx& x, int tag, L&& launch) {
 
 hipError_t timedBg(Ctx& x, int tag, const BgDev& p, const SrcDesc& src, const OutDesc& od, int C,
                    HistCopy* hc = nullptr) {
-    return timed(x, tag, [&] { return launchBg(p, src, od, C, x.s, hc); });
+    // the meter on and an integer PCM view (the fused store of a device call): the launch tallies what it stores
+    uint64_t* meter = (x.h->meterOn && pcmIsInt(od.pcm)) ? static_cast<uint64_t*>(x.h->meterBuf.p) : nullptr;
+    return timed(x, tag, [&] { return launchBg(p, src, od, C, x.s, hc, meter); });
 }
 
 SrcDesc mkSrc(const Hist& hs, int C, int64_t x0, const InView& in) {

@@ -267,6 +267,10 @@ struct gar_resampler {
     // gar_set_dither: configuration (not stream state, not in the state blob); the position is the group's statOut
     int32_t ditherMode = GAR_DITHER_NONE;
     uint64_t ditherSeed = 0;
+    // gar_set_meter: configuration like dither; meterBuf = [channels] x {uint64 clips, uint64 peak bits} in device
+    // memory, allocated when the meter is first turned on, zeroed by gar_reset and by gar_meter_read's reset
+    bool meterOn = false;
+    gar::DevBuf meterBuf;
     double fpInRate = 0, fpOutRate = 0;
     int32_t fpQuality = 0;  // engine.Quality of the engine constructors
     gar::DevBuf stateImg, stateTab;

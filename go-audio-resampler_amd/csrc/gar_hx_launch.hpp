@@ -75,7 +75,7 @@ int firTraceLines(const FirLaunchPlan& pl, const BgDev& p, const SrcDesc& src, c
 hipError_t launchBgPlan(const BgLaunchPlan& pl, const BgKnobs& k, const BgDev& p, const SrcDesc& src, const OutDesc& od,
                         hipStream_t stream, HistCopy* hc);
 hipError_t launchHxsPlan(const HxsLaunchPlan& pl, const HxsKnobs& k, const HxDev& p, const SrcDesc& src, const OutDesc& od, int C,
-                         hipStream_t stream, HistCopy* hc);
+                         hipStream_t stream, HistCopy* hc, uint64_t* meter = nullptr);
 hipError_t launchHxPlan(const HxLaunchPlan& pl, const HxKnobs& k, const HxDev& p, const SrcDesc& src, const OutDesc& od, int C,
                         hipStream_t stream);
 

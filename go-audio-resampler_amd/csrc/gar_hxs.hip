@@ -21,6 +21,7 @@ GAR_HXS_FOR_ALL(GAR_HXS_EXT)
 #define GAR_HXS_EXT_DITHER(NS, V) extern template hipError_t hxsLaunchDither<NS, V>(const HxsArgs&, size_t, int64_t, hipStream_t, int);
 GAR_HXS_FOR_DITHER(GAR_HXS_EXT_DITHER)
 #undef GAR_HXS_EXT_DITHER
+// the metered instantiations (declared in gar_hxs.hpp, defined in their units only): gar_hxs_i5.hip / gar_hxs_i6.hip
 // hxt_kernel instantiations: gar_hxt_i1.hip / gar_hxt_i2.hip
 #define GAR_HXT_EXT(NS, F, V, L) extern template hipError_t hxtLaunch<NS, F, V, L>(const HxsArgs&, size_t, int64_t, hipStream_t);
 GAR_HXT_FOR_A(GAR_HXT_EXT)
@@ -114,7 +115,12 @@ hipError_t hxtFmt(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, 
 }
 
 template <int NS>
-hipError_t hxsVst(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, int qWaves) {
+hipError_t hxsVst(const HxsArgs& x, size_t lds, int64_t blocks, hipStream_t st, int qWaves, uint64_t* meter) {
+    if (meter) {  // integer PCM output (launchHxsPlan): the two store layouts that take it
+        if (x.vst == kVstAny) return hxsLaunchMeter<NS, kVstAny>(x, meter, lds, blocks, st, qWaves);
+        if (x.vst == kVstStereoPcm16) return hxsLaunchMeter<NS, kVstStereoPcm16>(x, meter, lds, blocks, st, qWaves);
+        return hipErrorNotSupported;
+    }
     switch (x.vst) {
         case kVstAny:
             return x.dither ? hxsLaunchDither<NS, kVstAny>(x, lds, blocks, st, qWaves) : hxsLaunch<NS, kVstAny>(x, lds, blocks, st, qWaves);
@@ -191,7 +197,9 @@ HxsArgs hxsArgsOf(const HxsLaunchPlan& pl, const HxDev& p, const SrcDesc& src, c
 }  // namespace
 
 hipError_t launchHxsPlan(const HxsLaunchPlan& pl, const HxsKnobs& k, const HxDev& p, const SrcDesc& src, const OutDesc& od, int C,
-                         hipStream_t stream, HistCopy* hc) {
+                         hipStream_t stream, HistCopy* hc, uint64_t* meter) {
+    if (!pcmIsInt(od.pcm)) meter = nullptr;  // only the clamping stores are metered
+    if (meter && pl.kernel == HxsKernel::Hxt) return hipErrorNotSupported;  // hxt_kernel stores no PCM (its planner declines od.pcm)
     if (k.trace) {
         char line[512];
         hxsTraceLines(pl, od, C, line, sizeof(line));
@@ -218,7 +226,7 @@ hipError_t launchHxsPlan(const HxsLaunchPlan& pl, const HxsKnobs& k, const HxDev
         }
     }
     switch (p.NS) {
-#define GAR_HXS_NS(n) case n: return hxsVst<n>(x, pl.lds, blocks, stream, k.hxqW);
+#define GAR_HXS_NS(n) case n: return hxsVst<n>(x, pl.lds, blocks, stream, k.hxqW, meter);
 #if !GAR_HXS_QUICK
         GAR_HXS_NS(1) GAR_HXS_NS(2) GAR_HXS_NS(3) GAR_HXS_NS(4) GAR_HXS_NS(5) GAR_HXS_NS(6) GAR_HXS_NS(7)
         GAR_HXS_NS(8)

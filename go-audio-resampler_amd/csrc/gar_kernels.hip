@@ -107,7 +107,7 @@ int deviceCUs() {
 
 // Every x == 0 FIR launch: the CU count, the knobs, the plan (firPlanLaunch: which kernel family and its
 // geometry), then that family's dispatch, which traces from the plan, fills the arguments and launches.
-hipError_t launchBg(const BgDev& p, const SrcDesc& src, const OutDesc& od, int C, hipStream_t stream, HistCopy* hc) {
+hipError_t launchBg(const BgDev& p, const SrcDesc& src, const OutDesc& od, int C, hipStream_t stream, HistCopy* hc, uint64_t* meter) {
     if (od.o_hi <= od.o_lo) return hipSuccess;
     const int ncu = deviceCUs();
     const FirKnobs k = firLaunchKnobs();
@@ -115,9 +115,10 @@ hipError_t launchBg(const BgDev& p, const SrcDesc& src, const OutDesc& od, int C
     // a dithered PCM view is stored by the streaming kernels only (the engine fuses PCM where their planner never
     // declines, hxsPlanFits): any other route would truncate silently
     if (od.dither && pl.path != FirPath::Hxs) return hipErrorNotSupported;
+    if (meter && pl.path != FirPath::Hxs) return hipErrorNotSupported;  // nor would any other route tally
     switch (pl.path) {
         case FirPath::Bg: return launchBgPlan(pl.bg, k.bg, p, src, od, stream, hc);
-        case FirPath::Hxs: return launchHxsPlan(pl.hxs, k.hxs, *p.hx, src, od, C, stream, hc);
+        case FirPath::Hxs: return launchHxsPlan(pl.hxs, k.hxs, *p.hx, src, od, C, stream, hc, meter);
         case FirPath::Hx: return launchHxPlan(pl.hx, k.hx, *p.hx, src, od, C, stream);
         default: return hipSuccess;
     }
@@ -616,7 +617,7 @@ __global__ __launch_bounds__(256) void pack24_kernel(const T* s, uint8_t* d, int
 }
 
 hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs, void* dst, int d_type, int64_t d_fs,
-                         int64_t d_cs, int64_t n, int C, hipStream_t stream, const Dither& dz) {
+                         int64_t d_cs, int64_t n, int C, hipStream_t stream, const Dither& dz, uint64_t* meter) {
     if (n <= 0) return hipSuccess;
     // packed 24-bit, interleaved contiguous from a 4-byte aligned base, against contiguous f32 / f64 (16-B aligned):
     // the vector kernels (knob GAR_PACK24_VEC=0, read per launch for A/B timing: the per-element kernel)
@@ -624,6 +625,10 @@ hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs
     const uintptr_t sA = reinterpret_cast<uintptr_t>(src), dA = reinterpret_cast<uintptr_t>(dst);
     const bool unpackV = s_type == kSampPcm24P && d_type <= 1 && contig && (sA & 3) == 0 && (dA & 15) == 0;
     const bool packV = d_type == kSampPcm24P && s_type <= 1 && contig && (dA & 3) == 0 && (sA & 15) == 0;
+    if (meter && pcmIsInt(d_type)) {  // the metered kernels, by the same layout choice
+        const char* e = std::getenv("GAR_PACK24_VEC");
+        return launchConvertMeter(src, s_type, s_fs, s_cs, dst, d_type, d_fs, d_cs, n, C, stream, dz, meter, packV && (!e || std::atoi(e) != 0));
+    }
     if (unpackV || packV) {
         const char* e = std::getenv("GAR_PACK24_VEC");
         if (!e || std::atoi(e) != 0) {

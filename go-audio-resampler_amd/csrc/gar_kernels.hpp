@@ -127,6 +127,32 @@ __host__ __device__ inline int32_t pcmDitherAt(double y, int bits, uint32_t seed
     const uint32_t kh = ditherKeyHi(ditherKey(seedLo, seedHi, c), static_cast<uint32_t>(n >> 32));
     return pcmDitherOfF64(y, bits, ditherNoise(kh, static_cast<uint32_t>(n)));
 }
+// Clip / peak meter of an integer PCM store (gar.h gar_set_meter): THE tally of one stored sample,
+// called by every metered store path and by gar_dev_meter_tally.  y = the sample in the compute type, widened
+// exactly; `dither` with d = the sample's noise (ditherNoise) when the dithered quantizer stores it.  clips counts
+// y > 1 or y < -1 (+-Inf count, NaN does not) and, dithered, a floor(s + t) outside +-maxVal before its clamp
+// (pcmDitherOfF64's q, the same operations); peak = the largest |y| as the bit pattern of the non-negative double,
+// which orders like the value (NaN ignored, +Inf the largest).
+__host__ __device__ inline void meterTally(double y, int bits, bool dither, double d, uint32_t& clips, uint64_t& peak) {
+#pragma clang fp contract(off)
+    bool c = y > 1.0 || y < -1.0;
+    if (dither) {
+        const double m = pcmMax(bits);
+        const double v = y > 1.0 ? 1.0 : (y < -1.0 ? -1.0 : y);
+        const double q = __builtin_floor(v * m + (0.5 + d));
+        c = c || q > m || q < -m;
+    }
+    clips += c ? 1u : 0u;
+    const uint64_t a = __builtin_bit_cast(uint64_t, y) & 0x7fffffffffffffffull;
+    if (y == y && a > peak) peak = a;
+}
+// The tally of one sample from scratch: channel c at stream position n (the checked stores, the staged kernels).
+__host__ __device__ inline void meterTallyAt(double y, int bits, int dither, uint32_t seedLo, uint32_t seedHi, uint32_t c, uint64_t n,
+                                             uint32_t& clips, uint64_t& peak) {
+    double d = 0.0;
+    if (dither) d = ditherNoise(ditherKeyHi(ditherKey(seedLo, seedHi, c), static_cast<uint32_t>(n >> 32)), static_cast<uint32_t>(n));
+    meterTally(y, bits, dither != 0, d, clips, peak);
+}
 // One packed 24-bit sample at byte address b (no alignment): byte-wise, so nothing outside its 3 bytes is touched.
 __host__ __device__ inline int32_t pcm24Load(const uint8_t* b) {
     const uint32_t u = static_cast<uint32_t>(b[0]) | (static_cast<uint32_t>(b[1]) << 8) | (static_cast<uint32_t>(b[2]) << 16);
@@ -266,8 +292,10 @@ struct HistCopy {
 
 // Every x == 0 FIR stage: plans the launch (gar_hx_launch.hpp firPlanLaunch: the bg kernels, the streaming
 // split-f16 kernels or hx_kernel) and dispatches it.
+// `meter` (gar_set_meter on, an integer PCM view): the handle's tallies, [C] x {clips, peak bits}; the launch runs the
+// metered instantiations of the streaming kernels (gar_hxs_i5.hip), same plan, same stored bytes.
 hipError_t launchBg(const BgDev& p, const SrcDesc& src, const OutDesc& out, int C, hipStream_t stream,
-                    HistCopy* hc = nullptr);
+                    HistCopy* hc = nullptr, uint64_t* meter = nullptr);
 // True when a row-block plan fits the streaming kernels' geometry at one period per group (its smallest
 // ring), i.e. their planner never declines it (gar_hxs_launch.cpp).
 bool hxsPlanFits(const HxDev& p);
@@ -295,7 +323,11 @@ struct Dither {
     int64_t pos0 = 0;
 };
 hipError_t launchConvert(const void* src, int s_type, int64_t s_fs, int64_t s_cs, void* dst, int d_type, int64_t d_fs,
-                         int64_t d_cs, int64_t n, int C, hipStream_t stream, const Dither& dz = Dither());
+                         int64_t d_cs, int64_t n, int C, hipStream_t stream, const Dither& dz = Dither(), uint64_t* meter = nullptr);
+// `meter` (an integer PCM d_type): the metered kernels of gar_meter.hip store the same bytes by the same layout
+// choice and tally every stored sample of channel c into meter[2 * c], meter[2 * c + 1] (clips, peak bits).
+hipError_t launchConvertMeter(const void* src, int s_type, int64_t s_fs, int64_t s_cs, void* dst, int d_type, int64_t d_fs,
+                              int64_t d_cs, int64_t n, int C, hipStream_t stream, const Dither& dz, uint64_t* meter, bool packV);
 
 // One history of a state snapshot (gar_state_save / gar_state_load): `rows` rows of C elements of `es`
 // bytes, contiguous at `ptr` (leading dimension C, the engine's Hist layout), stored tightly packed from

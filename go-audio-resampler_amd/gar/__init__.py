@@ -93,6 +93,7 @@ EXPORTED = [
     "gar_synchronize", "gar_profile_launch_stats", "gar_profile_kinds", "gar_dev_half_convert",
     "gar_dev_pcm24_convert", "gar_dev_hxs_plan", "gar_dev_fir_plan", "gar_state_size", "gar_state_save", "gar_state_load",
     "gar_set_dither", "gar_get_dither", "gar_dev_dither_quantize",
+    "gar_set_meter", "gar_get_meter", "gar_meter_read", "gar_dev_meter_tally",
 ]
 
 _lib = None
@@ -169,6 +170,10 @@ def lib():
         "gar_set_dither": (i32, [vp, i32, C.c_uint64]),
         "gar_get_dither": (i32, [vp, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(i64)]),
         "gar_dev_dither_quantize": (i32, [i32, C.c_uint64, i32, i64, vp, i64, vp, vp]),
+        "gar_set_meter": (i32, [vp, i32]),
+        "gar_get_meter": (i32, [vp, C.POINTER(i32)]),
+        "gar_meter_read": (i32, [vp, i32, i32, vp, vp, i32]),
+        "gar_dev_meter_tally": (i32, [i32, i32, C.c_uint64, i32, i64, vp, i64, C.POINTER(C.c_uint64), C.POINTER(d)]),
     }
     ab = os.environ.get("GAR_LIB_PATH") is not None
     for name, (res, args) in sig.items():
@@ -385,6 +390,28 @@ class Resampler:
         _check(lib().gar_get_dither(self._h, C.byref(m), C.byref(s), C.byref(p)))
         return m.value, s.value, p.value
 
+    # -- clip counter / peak meter of the integer PCM output (gar.h gar_set_meter / gar_meter_read) --
+    def set_meter(self, on):
+        """on = True: every integer PCM sample process_device / flush_device store from now on updates the
+        channel's clip count and peak |y| in device memory (gar.h: the definition).  Configuration like
+        dither: survives Reset and load_state; Reset zeroes the tallies, load_state leaves them."""
+        _check(lib().gar_set_meter(self._h, int(on)))
+
+    def get_meter(self):
+        v = C.c_int32(0)
+        _check(lib().gar_get_meter(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def meter_read(self, ch0=0, n_ch=None, reset=False):
+        """(clips uint64 [n_ch], peak float64 [n_ch]) of channels ch0 .. ch0 + n_ch - 1 (default: to the last
+        channel), after waiting for the handle's enqueued calls; reset zeroes exactly those channels."""
+        if n_ch is None:
+            n_ch = self.Channels - ch0
+        clips = np.zeros(max(n_ch, 0), dtype=np.uint64)
+        peak = np.zeros(max(n_ch, 0), dtype=np.float64)
+        _check(lib().gar_meter_read(self._h, int(ch0), int(n_ch), _p(clips), _p(peak), int(bool(reset))))
+        return clips, peak
+
     def num_stages(self):
         return lib().gar_num_stages(self._h)
 
@@ -550,6 +577,16 @@ def dither_quantize(y, pcm_bits, seed, channel, position0):
     _check(lib().gar_dev_dither_quantize(int(pcm_bits), int(seed) & 0xFFFFFFFFFFFFFFFF, int(channel), int(position0),
                                          _p(y), y.size, _p(q), _p(d)))
     return q, d
+
+
+def meter_tally(y, pcm_bits, dither_mode, seed, channel, position0):
+    """Host run of the kernels' meter tally (gar.h gar_dev_meter_tally) on the float64 array y, taken as the samples
+    of channel `channel` from stream position position0: (clips, peak)."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    c, p = C.c_uint64(0), C.c_double(0)
+    _check(lib().gar_dev_meter_tally(int(pcm_bits), int(dither_mode), int(seed) & 0xFFFFFFFFFFFFFFFF, int(channel),
+                                     int(position0), _p(y), y.size, C.byref(c), C.byref(p)))
+    return c.value, p.value
 
 
 def half_convert(x, half_type):

@@ -268,6 +268,50 @@ enum { GAR_DITHER_NONE = 0, GAR_DITHER_TPDF = 1 };
 gar_status gar_set_dither(gar_resampler *r, int32_t mode, uint64_t seed);
 gar_status gar_get_dither(const gar_resampler *r, int32_t *mode, uint64_t *seed, int64_t *position);
 
+/* ---- clip counter and peak meter of the integer PCM output ----------------- */
+/* Every integer PCM store clamps to [-1, 1] first, and a resampled signal overshoots its input (a
+ * full-scale square through 44.1k -> 48k goes past 1.0).  The meter is opt-in and per handle.  While it
+ * is on, every integer PCM sample stored by gar_process_device / gar_flush_device (out_dtype
+ * GAR_PCM16 / 24 / 32 / GAR_PCM24_PACKED) updates two values per channel, kept in device memory and
+ * computed inside the kernels that store the sample, where the unclamped value still exists (after
+ * libsoxr's soxr_num_clips).  Let y be the sample in the compute type, widened exactly to float64:
+ *   - clips: uint64 count of stored samples that a clamp changed.  A sample is clipped when y > 1.0 or
+ *     y < -1.0; +-Inf count; NaN does not count (it stores 0 as ever).  With GAR_DITHER_TPDF on, a
+ *     sample is also clipped when q = floor(s + t) of the dither text above, taken before its clamp to
+ *     +-maxVal, lies outside [-maxVal, maxVal] (a sample at exactly +-1.0 whose noise pushes it over).
+ *   - peak: the maximum of |y| over the metered samples, a double.  It starts at 0, NaN is ignored,
+ *     +Inf is a legal value.
+ * Each stored sample is tallied exactly once, with the value that ends up in memory (an output the
+ * exact fallback recomputes is tallied with the recomputed value only), and turning the meter on does
+ * not change a stored byte.  Float and half outputs do not clamp and are not metered; host-memory calls
+ * are not metered.  Channels are the handle's channels (batch: stream * channels + ch, as for the
+ * dither keys).  The tallies accumulate across calls until read with reset or until gar_reset.
+ * The on / off setting is configuration, like dither: it applies to the device calls enqueued after
+ * gar_set_meter, survives gar_reset and gar_state_load and is not in the state blob (format and version
+ * unchanged).  gar_reset zeroes the tallies; gar_state_load leaves them alone (they describe what this
+ * handle stored, not the stream).  Dry-run handles accept both calls and read zeros.
+ * gar_set_meter: on = 0 / 1; anything else, or a NULL handle: GAR_ERR_INVALID_ARGUMENT, nothing changed.
+ *   The first gar_set_meter(r, 1) allocates the handle's tallies ([channels] x 16 bytes, zeroed).
+ * gar_get_meter: *on = the setting.
+ * gar_meter_read: waits for the handle's enqueued calls (gar_synchronize's wait; a raised device status
+ *   word gives GAR_ERR_DEVICE), then clips[i], peak[i] = the tallies of channel ch0 + i, i < n_ch; either
+ *   pointer may be NULL.  reset != 0 zeroes exactly those channels, ordered before any later call on the
+ *   handle.  A channel range outside the handle: GAR_ERR_INVALID_ARGUMENT, nothing read or reset.  A
+ *   handle whose meter was never on reads zeros.
+ * Waiting: the zeroing (gar_meter_read with reset, and gar_reset on a handle whose meter has ever been on,
+ *   also after it was turned off again: the tallies stay allocated) waits for the handle's enqueued calls
+ *   as gar_synchronize does -- for a handle used on one stream only that is a wait for the device, see
+ *   gar_process_device -- and then for a memset on the handle's own stream.  So gar_reset is no longer
+ *   free of synchronisation on such a handle; do not call either during a stream capture.
+ * A metered integer PCM store is served by the streaming FIR kernels or by the staged conversion kernels.
+ *   Should a launch plan route a fused PCM store to any other kernel (development knobs only; the engine
+ *   fuses PCM only where the streaming planner never declines), the call fails with a device error
+ *   rather than store without tallying -- as a dithered store does. */
+gar_status gar_set_meter(gar_resampler *r, int32_t on);
+gar_status gar_get_meter(const gar_resampler *r, int32_t *on);
+gar_status gar_meter_read(gar_resampler *r, int32_t ch0, int32_t n_ch, uint64_t *clips, double *peak,
+                          int32_t reset);
+
 /* ---- state snapshots (checkpoint / resume / migrate) ---------------------- */
 /* The streaming state of a handle -- every channel group with its channel range, the per-stage
  * counters (history lengths, polyphase position, decimator phase, cubic phase, fused / stage-by-stage
@@ -367,6 +411,14 @@ gar_status gar_dev_pcm24_convert(const double *in, int64_t n, uint8_t *packed, i
  * noise may each be NULL.  For tests (CPU suite). */
 gar_status gar_dev_dither_quantize(int32_t pcm_type, uint64_t seed, int32_t channel, int64_t position0,
                                    const double *in, int64_t n, int32_t *out, double *noise);
+
+/* The meter's tally of gar_set_meter run on the host (no GPU; the kernels call the same function):
+ * *clips, *peak = the tallies of in[0 .. n) stored as the samples of channel `channel` at stream
+ * positions position0 + i in pcm_type, with dither_mode GAR_DITHER_NONE or GAR_DITHER_TPDF (seed as
+ * gar_set_dither).  Another type or mode: GAR_ERR_INVALID_ARGUMENT.  Either output may be NULL.  For
+ * tests (CPU suite). */
+gar_status gar_dev_meter_tally(int32_t pcm_type, int32_t dither_mode, uint64_t seed, int32_t channel,
+                               int64_t position0, const double *in, int64_t n, uint64_t *clips, double *peak);
 
 /* The launch plan of the streaming FIR kernels for one call, computed on the host (no GPU; the
  * planner of every streaming launch, csrc/gar_hxs_launch.hpp): writes the GAR_HX_TRACE line(s) such a launch
